@@ -1,17 +1,31 @@
 """Headline benchmark: denoise-steps/sec at N=256, T=1000, batch=8 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one iteration of the reverse loop (genie/sampler/base.py:239-282)
 over one batch of 8 structures: Denoiser.forward + posterior update + Frenet
 frames, all inside libgenie_hip (genie_sample_loop), inputs resident in HBM.
+The W warm-up steps and then the K timed steps walk the loop's steps T, T-1,
+..., 1; when W + K exceeds T the walk starts a new pass at step T (a fresh
+trajectory from the same initial noise), so K sets the number of timed steps
+whatever its size.
 Each rank runs its own replica with its own noise seed (structures shard across
 GPUs with no data-path collective); the only collectives are the timing
 barrier / max and a trivial all_gather of the final C-alpha coordinates.
 
 Rank 0 prints ONE JSON line.  `value` = batch-steps/s summed over all ranks
-(x8 = structure-steps/s, also reported).  `roofline` prices the dominant kernel
+(x8 = structure-steps/s, also reported); `ms_per_step` = milliseconds of one
+timed step.  Weights, features and noise are seeded, so the same arguments give
+the same inputs on every run.  --dump-outputs DIR writes what the last timed
+step left, rank 0's replica: DIR/trans.npy [B,N,3] (C-alpha coordinates) and
+DIR/rots.npy [B,N,3,3] (Frenet frames), float32.
+
+A plain run measures only the headline figure: setup, warm-up, the K timed
+steps, the dump, the line.  Everything below takes runs of its own and comes
+only with --full (the --no-* options then leave parts of it out):
+`roofline`, `other_pair_kernel_rooflines`, `kernels` and `whole_step_hbm` come
+from an untimed pass with per-kernel HIP events.  `roofline` prices the dominant kernel
 class (largest time per step, HIP events on the launch stream) against the roof
 that bounds it: its algorithmic HBM bytes at 8 TB/s or its matrix FLOPs at the
 MFMA peak of the arithmetic in use, whichever takes longer (--math hx: three f16
@@ -20,7 +34,7 @@ MFMAs per f32 product at 2.5 PFLOP/s; --math f32: v_mfma_f32 at 157.3 TFLOP/s).
 WRITE_SIZE passes (profiles/), null if that kernel was not profiled.
 `cpu_baseline` times the oracle (the CPU restatement of the reference) on this
 host: 1 warm-up + 3 timed consecutive steps of the same workload, median.
-At N=1 the same line also carries `value_f32` (the same K steps in the exact-f32
+At N=1 the --full line also carries `value_f32` (the same K steps in the exact-f32
 MFMA kernels), `hx_vs_f32` (distance of the two trajectories after those steps)
 and `full_loop` (all T=1000 reverse steps of one batch, timed end to end), and `train_step` (BASELINE config 5's shape on one
 GPU: forward + backward + Adam of the base model at N=256, batch 2, f32-grade arithmetic, 1 warm-up + 5 timed steps).
@@ -31,6 +45,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -240,12 +255,18 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--length', type=int, default=256)
     ap.add_argument('--batch', type=int, default=8)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra-legs', action='store_true', help='skip the other-arithmetic and full T=1000 legs (N=1 only)')
-    ap.add_argument('--no-train-leg', action='store_true', help='skip the training-step leg (N=1 only)')
-    ap.add_argument('--profile-steps', type=int, default=3)
+    ap.add_argument('--full', action='store_true', help='also the per-kernel profile pass and roofline, and at N=1 the other-arithmetic, '
+                                                        'full T=1000, MFMA-probe, training-step and CPU-baseline legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write trans.npy and rots.npy (float32) of the last timed step, rank 0, into DIR')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU-baseline leg')
+    ap.add_argument('--no-extra-legs', action='store_true', help='with --full: skip the other-arithmetic and full T=1000 legs (N=1 only)')
+    ap.add_argument('--no-train-leg', action='store_true', help='with --full: skip the training-step leg (N=1 only)')
+    ap.add_argument('--profile-steps', type=int, default=3, help='with --full: steps of the per-kernel profile pass')
     ap.add_argument('--math', choices=['hx', 'f32'], default=None, help='pair-stack arithmetic (default: library default, hx)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     rank = int(os.environ.get('RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -264,7 +285,6 @@ def main():
     dims = dict(pack.BASE_DIMS)
     B, N, T = args.batch, args.length, dims['n_timestep']
     K, W = args.steps, args.warmup
-    assert K + W <= T, 'steps + warmup must fit in T'
     eng = GenieEngine(dims, pack.random_state_dict(dims, seed=0), dev, math=args.math)
     math = eng.math
     feats = F.convert_np_features_to_tensor(
@@ -287,17 +307,26 @@ def main():
             td.barrier()
         torch.cuda.synchronize(dev)
 
+    def walk(i, n, state):
+        """n reverse-loop steps from position i of the walk T, T-1, ..., 1, T, T-1, ...: one genie_sample_loop call per pass (a call
+        that starts at step T starts the trajectory afresh from noise[0])"""
+        while n > 0:
+            first = T - i % T
+            m = min(n, first)
+            tr, ro, _ = eng.sample_loop(noise, 0.6, first_step=first, last_step=first - m + 1, state=state)
+            state, i, n = (tr, ro), i + m, n - m
+        return state
+
     def timed_leg():
         """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides"""
         if W > 0:
-            tr, ro, _ = eng.sample_loop(noise, 0.6, first_step=T, last_step=T - W + 1)
-            state = (tr, ro)
+            state = walk(0, W, None)
         else:
             tr = noise[0].clone()
             state = (tr, eng.frenet(tr))
         barrier()
         t0 = time.perf_counter()
-        tr, ro, _ = eng.sample_loop(noise, 0.6, first_step=T - W, last_step=T - W - K + 1, state=state)
+        tr, ro = walk(W, K, state)
         barrier()
         return time.perf_counter() - t0, tr, ro
 
@@ -310,11 +339,31 @@ def main():
     finite = bool(torch.isfinite(tr).all().item())
 
     out = None
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'trans.npy'), tr.float().cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, 'rots.npy'), ro.float().cpu().numpy())
     if rank == 0:
         value = K * world / dt
+        span = f'reverse-loop steps {T - W}..{T - W - K + 1}' if K + W <= T else \
+            f'{K} reverse-loop steps after {W} warm-up steps, from step {T} down to 1 and again from {T}'
+        out = {
+            'metric': 'denoise-steps/sec (N=256, T=1000, batch=8)', 'value': value, 'unit': 'batch-steps/s',
+            'n_gpus': world, 'steps': K, 'warmup': W, 'ms_per_step': dt / K * 1e3, 'higher_is_better': True,
+            'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'f32' if math == 'f32' else 'f32 (pair-stack products as 3 f16 MFMAs on 2xf16-split operands, f32 accumulate)',
+            'data': 'synthetic', 'math': math,
+            'config': {'workload': f'unconditional N={N}, T={T}, batch={B} per GPU, random-init base Denoiser '
+                                   f'(15.7M params), scale=0.6, {span}',
+                       'parallelism': f'replica per GPU x{world}, no data-path collective'},
+            'structure_steps_per_s': value * B,
+            'whole_step_tflops': step_flops(dims, B, N) * (K / dt) / 1e12,
+            'finite': finite, 'cpu_baseline': None,
+        }
+    if rank == 0 and args.full:
         # per-kernel timing with HIP events on the launch stream (separate, untimed pass)
         eng.profile(True)
-        s0 = T - W - K
+        s0 = T - (W + K) % T
         if s0 - P < 1:
             s0 = T
         eng.sample_loop(noise, 0.6, first_step=s0, last_step=s0 - P + 1, state=(tr.clone(), ro.clone()))
@@ -350,27 +399,16 @@ def main():
         other_roofs = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in price(k).items()
                            if kk in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'avg_launch_ms')}
                        for k in flops if k in kern and k != dom}
-        whole = step_flops(dims, B, N) * (K / dt) / 1e12
         # algorithmic pair-tensor passes of the launches this step actually made (+ 8 IPA reads + 1 pair_init write)
         nbytes_step = sum(algorithmic_bytes(dims, B, N)[k] * v['launches_per_step'] for k, v in kern.items() if k in flops) \
             + 9 * 4.0 * B * N * N * dims['c_p']
-        out = {
-            'metric': 'denoise-steps/sec (N=256, T=1000, batch=8)', 'value': value, 'unit': 'batch-steps/s',
-            'n_gpus': world, 'steps': K, 'warmup': W, 'ms_per_step': dt / K * 1e3, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f32' if math == 'f32' else 'f32 (pair-stack products as 3 f16 MFMAs on 2xf16-split operands, f32 accumulate)',
-            'data': 'synthetic', 'math': math,
-            'config': {'workload': f'unconditional N={N}, T={T}, batch={B} per GPU, random-init base Denoiser '
-                                   f'(15.7M params), scale=0.6, reverse-loop steps {T - W}..{T - W - K + 1}',
-                       'parallelism': f'replica per GPU x{world}, no data-path collective'},
-            'structure_steps_per_s': value * B,
-            'whole_step_tflops': whole,
+        out.update({
             'whole_step_hbm': {'algorithmic_gb': nbytes_step / 1e9, 'achieved_gbs': nbytes_step / (dt / K) / 1e9,
                                'frac_of_8tbs': nbytes_step / (dt / K) / 1e9 / PEAK_HBM_GBS,
                                'unfused_reference_gb': 109 * 4.0 * B * N * N * dims['c_p'] / 1e9},
-            'finite': finite, 'roofline': roof, 'other_pair_kernel_rooflines': other_roofs,
+            'roofline': roof, 'other_pair_kernel_rooflines': other_roofs,
             'kernels': {k: {kk: round(vv, 4) for kk, vv in v.items()} for k, v in kern.items()},
-        }
+        })
         if world == 1 and not args.no_extra_legs:
             # (1) the same K steps in the exact-f32 MFMA kernels, from the same noise: rate, and how far the two arithmetics are apart
             other = 'f32' if math == 'hx' else 'hx'
@@ -407,8 +445,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(dims, B, N, 42)
             out['speedup_vs_cpu_baseline'] = value / out['cpu_baseline']['value']
-        else:
-            out['cpu_baseline'] = None
+    if rank == 0:
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)
         print(json.dumps(out), flush=True)

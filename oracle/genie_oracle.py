@@ -19,6 +19,7 @@ the reference root).  The code is written functionally over a flat
 `state_dict` with the reference's key names instead of
 the reference's nn.Module tree.
 """
+import contextlib
 import math
 
 import torch
@@ -135,6 +136,29 @@ def synthetic_state_dict(dims, seed=0):
             t = std * torch.randn(shape, generator=g)
         sd[key] = t.float().contiguous()
     return sd
+
+
+@contextlib.contextmanager
+def correctly_rounded_sqrt():
+    """torch.sqrt as the correctly rounded square root while the block runs: a float32 operand goes through float64 and is
+    rounded once, which is exact (53 >= 2 * 24 + 2 bits) and keeps autograd.  torch's own float32 sqrt goes through MKL, whose
+    last bit depends on the host CPU, so bit-exact fixtures that pass through sqrt (the frames in tests/golden/geometry.npz, the
+    schedule and noising in train_ends_n24_b4.npz) were made from the reference under this and are checked under it.
+    It replaces the module attribute, so it covers calls spelled `torch.sqrt(x)` only, not `x.sqrt()`, `x ** 0.5` or
+    `torch.norm`: the frames and schedule of the oracle and of the reference (geo_utils.py, ddpm.py) spell it so, and code
+    under this that must stay bit-exact has to keep that spelling."""
+    sqrt = torch.sqrt
+
+    def rn(x, *args, **kwargs):
+        if not args and not kwargs and torch.is_tensor(x) and x.dtype == torch.float32:
+            return sqrt(x.double()).float()
+        return sqrt(x, *args, **kwargs)
+
+    torch.sqrt = rn
+    try:
+        yield
+    finally:
+        torch.sqrt = sqrt
 
 
 # --------------------------------------------------------------------------

@@ -226,14 +226,15 @@ def test_handle_free_frenet_frames_matches_reference_golden():
 def test_bench_emits_one_contract_line():
     """bench.py's contract with the driver: exactly ONE line on stdout, JSON, with the keys the driver and the judge read (metric /
     value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload,
-    the roofline object).  Short run (2 steps), without the CPU-baseline and extra legs; then the same through the 1-rank RCCL path."""
+    the roofline object of --full).  Short run (2 steps), without the CPU-baseline and extra legs; then the same through the 1-rank
+    RCCL path."""
     import json
     import os
     import subprocess
     import sys
     from conftest import ROOT
     for extra_env in ({}, {'GENIE_BENCH_FORCE_DIST': '1', 'RANK': '0', 'WORLD_SIZE': '1', 'LOCAL_RANK': '0', 'MASTER_ADDR': '127.0.0.1', 'MASTER_PORT': '29597'}):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-extra-legs',
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-extra-legs',
                             '--profile-steps', '1'], capture_output=True, text=True, timeout=600, env=dict(os.environ, **extra_env), cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -249,3 +250,45 @@ def test_bench_emits_one_contract_line():
         for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic'):
             assert k in rf, k
         assert rf['bound'] in ('hbm', 'mfma') and abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-9 and 0 < rf['frac'] < 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run (no --full): the one contract line without the profile pass or any extra leg, exactly --steps timed
+    steps, and --dump-outputs writing what the last timed step left as float32 arrays.  Two runs with the same arguments dump
+    the same bits (seeded inputs).  The walk starts over at step T after step 1: 2 timed steps after a whole pass of warm-up,
+    and 998 + 4 steps that end with steps T and T - 1 of a new pass, are bit for bit what 2 steps without warm-up give (a dump
+    of the warm-up state, which differs between these runs, would fail that); one more timed step changes the dump."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    T = 1000
+
+    def run(steps, warmup, name):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', str(warmup), '--dump-outputs',
+                            str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines[:5]
+        d = json.loads(lines[0])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in d, k
+        assert d['steps'] == steps and d['warmup'] == warmup and d['finite'] is True and d['cpu_baseline'] is None
+        assert abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value'] and d['value'] > 10
+        for k in ('roofline', 'kernels', 'train_step', 'full_loop', 'value_f32'):
+            assert k not in d, k
+        trans, rots = np.load(out / 'trans.npy'), np.load(out / 'rots.npy')
+        assert trans.dtype == np.float32 and trans.shape == (8, 256, 3) and np.isfinite(trans).all()
+        assert rots.dtype == np.float32 and rots.shape == (8, 256, 3, 3) and np.isfinite(rots).all()
+        return trans, rots
+
+    a = run(4, T - 2, 'a')                    # warm-up and timed steps together cross step 1
+    b = run(4, T - 2, 'b')
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    wrapped, fresh = run(2, T, 'wrapped'), run(2, 0, 'fresh')
+    assert all(np.array_equal(x, y) for x, y in zip(wrapped, fresh))
+    assert all(np.array_equal(x, y) for x, y in zip(a, fresh))
+    assert not np.array_equal(run(3, 0, 'one_more')[0], fresh[0])

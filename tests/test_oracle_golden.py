@@ -30,6 +30,7 @@ def test_encoding_matches_reference():
         assert abs(float(e.double().sum()) - float(g[nm + '_sum'])) < 1e-6
 
 
+@O.correctly_rounded_sqrt()          # the fixture's frames were made under it: host-independent bits (genie_oracle.py)
 def test_frenet_matches_reference():
     g = load_golden('geometry')
     r = O.compute_frenet_frames(t(g['frenet_coords']), t(g['frenet_chains']), t(g['frenet_mask']))
@@ -93,6 +94,7 @@ def _train_features(g):
     return f
 
 
+@O.correctly_rounded_sqrt()          # as the fixture was made: schedule and frames with host-independent bits
 def test_training_step_ends_match_reference_golden():
     """The two ends of Genie.training_step around the denoiser (diffusion/genie.py:77-105): forward noising + frames and
     the loss with its gradient, against what the reference's own get_betas / compute_frenet_frames / mse + autograd gave."""

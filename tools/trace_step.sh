@@ -4,7 +4,7 @@ TAG=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/trace_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/raw" -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs --profile-steps 1 > "$OUT/log.txt" 2>&1 || { tail -5 "$OUT/log.txt"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/raw" -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs --profile-steps 1 > "$OUT/log.txt" 2>&1 || { tail -5 "$OUT/log.txt"; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]

@@ -2,7 +2,7 @@
 # GPU box: rocprofv3 kernel trace of a few reverse-loop steps; start offset / duration / queue of every kernel of the last structure net
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/trace_tl; rm -rf $OUT; mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extra-legs --profile-steps 1 > $OUT/log.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extra-legs --profile-steps 1 > $OUT/log.txt 2>&1
 python3 - <<'PY'
 import csv, glob
 f = glob.glob('gpurun_out/trace_tl/**/*kernel_trace.csv', recursive=True)[0]
