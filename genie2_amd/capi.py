@@ -90,6 +90,9 @@ SYMBOLS = {
                                      C.POINTER(C.c_int64), C.c_int]),
     'genie_probe_mfma': (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'genie_workspace_bytes': (C.c_size_t, [C.c_void_p]),
+    'genie_motif_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'genie_motif_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 _lib = None

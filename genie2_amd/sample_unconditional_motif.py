@@ -1,0 +1,116 @@
+"""`python -m genie2_amd.sample_unconditional_motif` -- motif-guided twisted-diffusion / SMC sampling, the fork's
+genie/sample_unconditional_motif.py (:131-166 flags; its runner drives genie/sampler/unconditional_smc.py) with the reference's
+flags and the unconditional CLI's output layout, outdir/pdbs/{length}_{index}.pdb.
+
+The reference hard-codes its motif (sampler/smc_sampler_new.py:155-157); here it is an explicit `--motif_file` in the REMARK 999
+format of the scaffold CLI.  Its motif entries, in file order, are the segments; their C-alpha coordinates come from the file's
+ATOM records.  Each batch is one particle system of `batch_size` particles guided by the fused motif potential (MotifPotential,
+csrc/smc_kernels.hip) over every placement of the segments in a structure of that length."""
+import argparse
+import os
+
+from tqdm import tqdm
+
+from .diffusion import load_pretrained_model
+from .motif import load_motif_spec
+from .sample_unconditional import UnconditionalRunner
+
+
+def load_motif_segments(filepath):
+    """The motif entries of a problem file, in file order, as [n_i, 3] lists of C-alpha coordinates (chain, residue index from
+    the ATOM records' columns 22 and 23-26, coordinates from 31-54, as features.parse_pdb reads them)."""
+    ca = {}
+    with open(filepath) as fh:
+        for line in fh:
+            if line.startswith('ATOM') and line[13:15].strip() == 'CA':
+                ca[(line[21], int(line[22:26]))] = [float(line[30:38]), float(line[38:46]), float(line[46:54])]
+    segments = []
+    for st in load_motif_spec(filepath)['structures']:
+        if st['type'] != 'motif':
+            continue
+        missing = [i for i in range(st['start_index'], st['end_index'] + 1) if (st['chain'], i) not in ca]
+        if missing:
+            raise ValueError('%s: no CA record for chain %s residue(s) %s' % (filepath, st['chain'], missing))
+        segments.append([ca[(st['chain'], i)] for i in range(st['start_index'], st['end_index'] + 1)])
+    if not segments:
+        raise ValueError('%s: no motif segment (REMARK 999 INPUT with a chain)' % filepath)
+    return segments
+
+
+class MotifRunner(UnconditionalRunner):
+    def create_tasks(self, params):
+        total = sum(len(s) for s in load_motif_segments(params['motif_file']))
+        tasks = super().create_tasks(params)
+        short = [t['length'] for t in tasks if t['length'] < total]
+        if short:
+            print('skipping lengths shorter than the {}-residue motif: {}'.format(total, ', '.join(map(str, short))))
+        return [t for t in tasks if t['length'] >= total]
+
+    def create_constants(self, params):
+        c = super().create_constants(params)
+        c.update({k: params[k] for k in ('tausq', 'guidance_alpha', 'ess_threshold', 'last_unguided_steps', 'max_offsets')})
+        c['segments'] = load_motif_segments(params['motif_file'])
+        return c
+
+    def execute(self, constants, tasks, device):
+        from . import pack
+        from .smc import MotifPotential, TwistedSampler
+        model = load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
+        sampler = TwistedSampler(model)
+        abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
+        for task in tqdm(tasks, desc=device):
+            remaining = constants['num_samples']
+            while remaining > 0:
+                batch = min(constants['batch_size'], remaining)
+                offset = constants['num_samples'] - remaining
+                if constants.get('resume') and all(
+                        os.path.exists(os.path.join(constants['outdir'], 'pdbs', '{}_{}.pdb'.format(task['length'], offset + i)))
+                        for i in range(batch)):
+                    remaining -= batch           # this batch was written by an earlier (interrupted) run
+                    continue
+                # one particle system per batch; its placements drawn from numpy's global generator, as the reference does
+                potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
+                                           max_offsets=constants['max_offsets'], device=device)
+                sampler.sample({
+                    'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
+                    'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
+                    'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
+                    'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps']})
+                remaining -= batch
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument('--name', type=str, help='Model name', required=True)
+    p.add_argument('--epoch', type=int, help='Model epoch', required=True)
+    p.add_argument('--rootdir', type=str, help='Root directory', default='results')
+    p.add_argument('--scale', type=float, help='Sampling noise scale', required=True)
+    p.add_argument('--outdir', type=str, help='Output directory', required=True)
+    p.add_argument('--num_samples', type=int, help='Number of samples per length', default=5)
+    p.add_argument('--batch_size', type=int, help='Batch size', default=4)
+    p.add_argument('--min_length', type=int, help='Minimum sequence length', default=50)
+    p.add_argument('--max_length', type=int, help='Maximum sequence length', default=256)
+    p.add_argument('--length_step', type=int, help='Length step size', default=1)
+    p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
+    p.add_argument('--sequential_order', action='store_true', help='Run in increasing order of length')
+    p.add_argument('--motif_file', type=str, required=True,
+                   help='Motif problem file (REMARK 999 format, as the scaffold CLI reads); its motif segments guide sampling '
+                        '(not in the reference CLI)')
+    p.add_argument('--tausq', type=float, default=0.012, help='Motif likelihood variance tau^2 (not in the reference CLI)')
+    p.add_argument('--guidance_alpha', type=float, default=0.012, help='Guidance gradient regulariser alpha (not in the reference CLI)')
+    p.add_argument('--ess_threshold', type=float, default=0.5,
+                   help='Resample when the effective sample size falls below this fraction of the batch (not in the reference CLI)')
+    p.add_argument('--last_unguided_steps', type=int, default=50,
+                   help='Steps below this one are not guided (not in the reference CLI)')
+    p.add_argument('--max_offsets', type=int, default=1000,
+                   help='Placements of the motif kept (a random subset when there are more) (not in the reference CLI)')
+    p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist (not in the reference CLI)')
+    return p
+
+
+def main(args):
+    MotifRunner().run(vars(args), args.num_devices, args.sequential_order)
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

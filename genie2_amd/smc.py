@@ -2,7 +2,8 @@
 `genie/sampler/unconditional_smc.py` (:25-43 weight helpers, :233-288 systematic resampling, :303-345 the motif twisting
 function, :465-576 the loop) without its wandb / file logging.  The gradient torch.autograd takes there through the whole
 Denoiser is `GenieEngine.denoise_vjp` here (HIP backward kernels, frames held fixed exactly as `T(rots.detach(), trans.detach())`
-does); the potential itself acts on a [B, N, 3] tensor and stays in PyTorch.
+does); the reference's potential acts on a [B, N, 3] tensor and stays in PyTorch here (motif_twisting_function), with
+MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -187,3 +188,101 @@ class TwistedSampler(UnconditionalSampler):
             rots = eng.frenet(trans)
         feats['atom_positions'] = trans.detach().cpu()
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
+
+
+def placement_starts(locs):
+    """get_all_motif_locations' output ([(start, end), ...] per placement) -> int32 [P, S], the start residue of every segment in
+    every placement, in the same order: what genie_motif_potential takes instead of the [P, N] masks of placement_masks."""
+    if not locs:
+        return torch.zeros(0, 0, dtype=torch.int32)
+    return torch.tensor([[st for st, _ in pl] for pl in locs], dtype=torch.int32)
+
+
+def _check_starts(starts, seg_len, n_res):
+    """The contract of genie_motif_potential, checked once on the host: segments in order, without overlap, inside 0..n_res-1."""
+    lens = torch.as_tensor(seg_len, dtype=torch.int64)
+    st = starts.to(torch.int64)
+    if st.dim() != 2 or st.shape[0] < 1 or st.shape[1] != len(lens):
+        raise ValueError('starts must be [P >= 1, %d], got %s' % (len(lens), tuple(starts.shape)))
+    ends = st + lens[None]                                          # one past each segment
+    if bool((st[:, 0] < 0).any()) or bool((ends[:, -1] > n_res).any()) or bool((ends[:, :-1] > st[:, 1:]).any()):
+        raise ValueError('a placement leaves 0..%d or puts its segments out of order' % (n_res - 1))
+
+
+class _MotifPotentialFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, pot, var):
+        logp, grad = pot._launch(x0, var)
+        ctx.save_for_backward(grad)
+        return logp
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        grad, = ctx.saved_tensors
+        return grad_output[:, None, None] * grad, None, None
+
+
+class MotifPotential:
+    """The motif twisting function of unconditional_smc.py:303-345 (motif_twisting_function above) as one HIP pass over every
+    placement: `pot(x0 [B,N,3], step) -> log p(y | x0) [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler.
+
+    The placements are enumerated (and thinned to `max_offsets` with one choice() draw of `rng`, numpy's global generator by default)
+    exactly as generate_motif_index_mask does, the concatenated target is centred as TwistedSampler centres it, and both are uploaded
+    once.  The forward launches genie_motif_potential on torch's current stream and keeps the gradient it computes; the backward
+    scales it.  Nothing on the per-step path reads device memory from the host: var = xstart_variance(alphas_cumprod[step], tausq)
+    stays on the device."""
+
+    def __init__(self, segments, n_res, alphas_cumprod, tausq=0.012, max_offsets=1000, rng=None, device='cuda'):
+        from . import capi
+        self.lib = capi.load_library()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise capi.GenieError('MotifPotential runs on the GPU (libgenie_hip); there is no CPU path')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        segs = [torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3) for x in segments]
+        self.seg_len = [len(x) for x in segs]
+        if not segs or min(self.seg_len) < 1:
+            raise ValueError('the motif needs at least one segment of at least one residue')
+        self.n_res, self.tausq = int(n_res), float(tausq)
+        self.locs = get_all_motif_locations(self.n_res, self.seg_len, max_offsets, rng)
+        if not self.locs:
+            raise ValueError('a motif of %d residues does not fit in %d' % (sum(self.seg_len), self.n_res))
+        starts = placement_starts(self.locs)
+        _check_starts(starts, self.seg_len, self.n_res)
+        self.P, self.S, self.M = starts.shape[0], starts.shape[1], sum(self.seg_len)
+        self.starts = starts.to(self.device)
+        self.seg_len_t = torch.tensor(self.seg_len, dtype=torch.int32, device=self.device)
+        tgt = torch.cat(segs).to(self.device)
+        self.target = (tgt - tgt.mean(dim=0, keepdim=True)).contiguous()      # (as TwistedSampler, smc.py:133-140)
+        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
+        self._work = torch.zeros(0, dtype=torch.uint8, device=self.device)
+
+    def variance(self, step):
+        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
+
+    def __call__(self, x0, step):
+        return _MotifPotentialFn.apply(x0, self, self.variance(step))
+
+    def _launch(self, x0, var):
+        import ctypes as C
+        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
+            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
+        if x0.device != self.device:
+            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
+        x = x0.detach().to(torch.float32).contiguous()
+        B = x.shape[0]
+        need = self.lib.genie_motif_potential_work_bytes(B, self.P)
+        if need > self._work.numel():
+            self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
+        logp = torch.empty(B, dtype=torch.float32, device=x.device)
+        grad = torch.empty_like(x)
+        p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
+        with torch.cuda.device(x.device):
+            rc = self.lib.genie_motif_potential(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
+                                                self.P, self.S, self.M, p(self.seg_len_t), p(self.starts), p(self.target), p(var),
+                                                p(logp), p(grad), p(self._work) if need else C.c_void_p(0), self._work.numel())
+        if rc != 0:
+            from . import capi
+            raise capi.GenieError('genie_motif_potential failed (%d)' % rc)
+        return logp, grad

@@ -132,6 +132,25 @@ int genie_frenet(genie_handle_t h, genie_stream_t stream, const float* trans /*[
 int genie_frenet_frames(genie_stream_t stream, int B, int N, const float* coords /*[B,N,3]*/, const int32_t* chains,
                         const int32_t* mask, float* rots_out /*[B,N,3,3]*/);
 
+/* The motif potential of twisted-diffusion / SMC sampling with its gradient, without a handle: the fork's motif twisting function
+ * (genie/sampler/unconditional_smc.py:303-345; genie2_amd/smc.py:58-69 restates it in PyTorch), one pass over every placement
+ * instead of a Python loop and an autograd walk back through it.  Placement p puts segment s at residues
+ * starts[p,s] .. starts[p,s] + seg_len[s] - 1 (in order, without overlap, inside 0..N-1: the caller validates `starts` once when it
+ * builds it); motif position m runs over the segments in order, as x0[:, mask] selects.  With M = sum seg_len:
+ *   c_bp(m) = x0[b, r_p(m)] - mean_m x0[b, r_p(m)],   e_bp(m) = c_bp(m) - target[m]
+ *   score[b,p] = -sum_m |e_bp(m)|^2 / (2 var),        logp_out[b] = logsumexp_p score[b,p] - log P
+ *   grad_out[b,n] = d logp[b] / d x0[b,n] = -sum_p w_bp [n in p] (e_bp(m_p(n)) - mean_m e_bp(m)) / var,  w_bp = softmax_p score[b,:]
+ * (exactly 0 at residues no placement covers).  `var` is one float in device memory (the sampler computes it on the device).
+ * seg_len, starts, target: device int32 [S], int32 [P,S], f32 [M,3].  One launch, or two when P is large enough that the placement
+ * scores spill to `work` (genie_motif_potential_work_bytes(B, P) bytes, 16-byte aligned; 0 = none needed, `work` may be NULL).
+ * No allocation, no synchronisation; bitwise reproducible (no atomics: the gradient is gathered per residue in a fixed order).
+ * Returns 0, or -1 for an impossible shape (P, S or M < 1, M > N, too little work) or a problem that does not fit in LDS. */
+int genie_motif_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int P, int S, int M,
+                          const int32_t* seg_len /*[S]*/, const int32_t* starts /*[P,S]*/, const float* target /*[M,3]*/,
+                          const float* var /*[1], device*/, float* logp_out /*[B]*/, float* grad_out /*[B,N,3]*/, void* work,
+                          size_t work_bytes);
+size_t genie_motif_potential_work_bytes(int B, int P);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
