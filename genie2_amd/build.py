@@ -18,7 +18,7 @@ SOURCES = ['pair_kernels.hip', 'pair_wl_kernels.hip', 'pair_hx_kernels.hip', 'pa
 HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'hx.h'), os.path.join(CSRC, 'hx_pair.h'), os.path.join(CSRC, 'hx_fused.h'), os.path.join(CSRC, 'train.h'), os.path.join(HERE, '..', 'include', 'genie_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function', '-Wno-unused-value',
-         '-DGENIE_BUILD'] + os.environ.get('GENIE_EXTRA_FLAGS', '').split()
+         '-DGENIE_BUILD']
 
 
 def _newer(target, deps):
@@ -46,7 +46,7 @@ def build(force=False):
     os.makedirs(LIBDIR, exist_ok=True)
     if force:
         for f in os.listdir(LIBDIR):
-            if os.path.isfile(os.path.join(LIBDIR, f)):      # (lib/abl/ holds developer variant builds)
+            if os.path.isfile(os.path.join(LIBDIR, f)):
                 os.remove(os.path.join(LIBDIR, f))
     with ThreadPoolExecutor(max_workers=4) as ex:
         objs = list(ex.map(_compile, SOURCES))

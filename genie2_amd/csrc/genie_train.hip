@@ -109,23 +109,7 @@ struct Run {
         if (dry) return;
         h->train_gemm_flop += 2.0 * p.M * p.N * (double)p.K * p.batch;
         ProfScope ps_(h, st, KC_TR_GEMM);
-#ifndef GENIE_DEV
         launch_gemm(st, p, terms);
-#else
-        static const bool log = getenv("GENIE_TRAIN_GEMM_LOG") != nullptr;      // developer aid (-DGENIE_DEV builds): one line per GEMM with its own duration; synchronises
-        if (!log) { launch_gemm(st, p, terms); return; }
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, st);
-        launch_gemm(st, p, terms);
-        (void)hipEventRecord(e1, st);
-        (void)hipEventSynchronize(e1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        fprintf(stderr, "GEMM M %d N %d K %d batch %d nsplit %d ak %lld bk %lld cn %lld mode %d us %.1f\n", p.M, p.N, p.K, p.batch, p.nsplit, p.ak, p.bk,
-                p.cn, p.mode, ms * 1e3f);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-#endif
     }
     // Y[R][O] = X[R][K] (ld ldx) W[O][K]^T + b
     void lin_fwd(const float* X, long long ldx, long long R, int K, size_t w, long long b_off, int O, float* Y, int mode = 0, bool relu = false) {

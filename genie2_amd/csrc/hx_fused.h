@@ -1,6 +1,5 @@
-// Shared by the fused pair-chain kernels (pair_fused_kernels.hip; the two-groups-per-CU variant measured in round 3 is kept as text
-// under tools/probe/attic/): launch arguments, the bias table's slots, the z staging helpers and the LayerNorm / split of
-// a result tile.  Layout conventions: pair_fused_kernels.hip's header comment.
+// Shared by the fused pair-chain kernels (pair_fused_kernels.hip): launch arguments, the bias table's slots, the z staging helpers
+// and the LayerNorm / split of a result tile.  Layout conventions: pair_fused_kernels.hip's header comment.
 #pragma once
 #include "hx_pair.h"
 
@@ -11,10 +10,9 @@
 #define FZ_SB_BP 896
 #define FZ_SB_FLOATS 1408
 #define FZ_OOR 0x7FFFFFF0
-#ifndef FZ_SAFE
-#define FZ_SAFE 0
-#endif
-#define FZ_FULL_WAIT(bit) do { if (FZ_SAFE & (bit)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); else asm volatile("" ::: "memory"); } while (0)
+// A compiler-only memory fence (no instruction): no memory access moves across it, which holds the z store in its place in the
+// schedule
+#define FZ_COMPILER_FENCE() asm volatile("" ::: "memory")
 
 struct FusedArgs {
     float* z; const float* xcm; const float* rmask; const unsigned char* wimg;
@@ -23,7 +21,7 @@ struct FusedArgs {
     int N, NP, n_wtiles, n_hb;
     unsigned cm_bytes, z_bytes;
     float sx, cgo, cz, c1, c2, inv_c2, cpa, cpb, cg;
-    int rev, stagger;
+    int rev;
 };
 
 // granules (16 B = 4 channels) g and g + 2 of this lane's row: the chained-k slots e = 0..3 / 4..7 of k-chunk 4 half + q
@@ -48,7 +46,7 @@ __device__ __forceinline__ void fz_zt_chunk(float4& a, float4& b, const unsigned
 __device__ __forceinline__ void fz_store_half(rsrc_t rz, unsigned char* zt, const f32x16& v0, const f32x16& v1, int lane, int soff,
                                               int row_stride, int nvalid, int hf) {
     const int pl = lane & 31, h = lane >> 5;
-    FZ_FULL_WAIT(1);
+    FZ_COMPILER_FENCE();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const f32x16& v = (q < 2) ? v0 : v1;
@@ -71,7 +69,7 @@ __device__ __forceinline__ void fz_store_half(rsrc_t rz, unsigned char* zt, cons
         // keeps `d` allocated until two wait states behind the store.
         asm volatile("s_nop 1" : "+v"(d) : : "memory");
     }
-    FZ_FULL_WAIT(2);
+    FZ_COMPILER_FENCE();
 }
 
 // LayerNorm statistics of a result tile (this lane's 64 channels + its partner's): mean and sx / sqrt(var + eps)

@@ -28,27 +28,6 @@ __device__ __forceinline__ float hx_load(rsrc_t r, int voff, int soff) {
 #define PIPE_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define HX_ZT_BYTES 8192                                   // per-wave row-tile staging (half a tile: 32 rows x 64 channels)
 #define HX_LDS_BYTES (2 * HX_STAGE_BYTES + 2048 + 8 * HX_ZT_BYTES)
-#ifndef HX_ABL
-#define HX_ABL 0          // developer builds (tools/abl_build.sh): 128 = in-kernel timestamps; 0 in the product
-#endif
-#if HX_ABL & 128          // in-kernel timestamps of every wave of work-group 0 (tests/devtools/ts_read.py)
-__device__ unsigned long long g_hx_ts[24][4096];   // [variant * 8 + wave]
-#define HX_TS_DECL(variant) const bool ts_on = blockIdx.x == 0; \
-                   unsigned long long* ts_p = g_hx_ts[(variant) * 8 + (threadIdx.x >> 6)]; int ts_n = 0
-#define HX_TS() do { if (ts_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63) == 0 && ts_n < 4096) ts_p[ts_n] = t_; ++ts_n; } } while (0)
-extern "C" int genie_hx_debug_read(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hx_ts), sizeof(unsigned long long) * 24 * 4096);
-}
-#if HX_ABL & 256          // finer stamps: per k-chunk in the projection (tests/devtools/ts_kc.py), inside the transition's first GEMM (tests/devtools/ts_tr.py)
-#define HX_TS2() HX_TS()
-#else
-#define HX_TS2() do { } while (0)
-#endif
-#else
-#define HX_TS_DECL(variant)
-#define HX_TS() do { } while (0)
-#define HX_TS2() do { } while (0)
-#endif
 
 __device__ __forceinline__ void hx_stage_landed() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -151,7 +130,7 @@ __device__ __forceinline__ void hx_vm_done() { asm volatile("s_waitcnt vmcnt(0)"
             PIPE_FENCE(); MFH(gq, zh[kc], AG); PIPE_FENCE(); HX_PROJ_PIECE_A(EG, 2 * kc + 1, t1);                  \
             PIPE_FENCE(); MFH(gh, zl[kc], AG); PIPE_FENCE(); HX_PROJ_PIECE_B(EP, 2 * kc + 1, t1, u1);              \
             PIPE_FENCE(); MFH(gh, zh[kc], AG); PIPE_FENCE(); HX_PROJ_PIECE_C(2 * kc + 1, t1, u1); HX_PROJ_REINIT(EP, EG, 2 * kc + 1); \
-            PIPE_FENCE(); HX_TS2();                                                                                \
+            PIPE_FENCE();                                                                                         \
             ph = nph; pq = npq; gh = ngh; gq = ngq;                                                                \
         }                                                                                                          \
     } while (0)

@@ -27,42 +27,6 @@
 #include "hx_fused.h"
 
 #define FZ_LDS_BYTES (2 * HX_STAGE_BYTES + 6144 + 8 * HX_ZT_BYTES)
-#ifndef FZ_XPRE
-#define FZ_XPRE 0          // 1: chain B fetches half of the next tile's x between the MFMAs of its last transition stages (32 registers held through the projections: 92 spills, 0.877 ms); 0: all of x at the tile's start (55 spills, 0.848 ms)
-#endif
-#ifndef FZ_ASYM
-#define FZ_ASYM 1          // 1: a stage's LDS-DMA pieces are all issued by waves 4..7 (their SIMD partners start the stage's MFMAs at once); 0: four pieces per wave.  +0.5 % on the step
-#endif
-#ifndef FZ_BIASPRE
-#define FZ_BIASPRE 1       // 1: a transition stage's initial accumulators (b1 block) are fetched under the previous stage's second GEMM (their registers are dead there): removes the kernels' last spills
-#endif
-#ifndef FZ_KO
-#define FZ_KO 0            // developer knock-outs of the transition stage (timing only, results wrong): 1 no ReLU / split, 2 no fragment re-reads, 4 no barrier / wait, 8 no weight DMA
-#endif
-#ifndef FZ_ZEARLY
-#define FZ_ZEARLY 0        // 1: the first channel half of z is requested at the tile's start (behind the x loads), not inside the first stage.  Measured: no gain -- the x loads take as much longer as the first stage gets shorter (the tile's bytes, not their latency, set both)
-#endif
-
-// developer builds (-DFZ_TS): s_memtime stamps of every wave of work-group 0, read with tests/devtools/ts_fused.py; none in the product
-#ifdef FZ_TS
-__device__ unsigned long long g_fz_ts[16][2048];      // [variant * 8 + wave]
-extern "C" int genie_fz_debug_read(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fz_ts), sizeof(unsigned long long) * 16 * 2048); }
-#define FZ_TS_DECL() const bool ts_on = blockIdx.x == 0 && HAS_P;      /* (the last block's chain without projections would overwrite chain B's slots) */ unsigned long long* ts_p = g_fz_ts[(HAS_T ? 8 : 0) + (threadIdx.x >> 6)]; int ts_n = 0
-#define FZ_STAMP() do { if (ts_on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if ((threadIdx.x & 63) == 0 && ts_n < 2048) ts_p[ts_n] = t_; ++ts_n; } } while (0)
-#else
-#define FZ_TS_DECL()
-#define FZ_STAMP() do { } while (0)
-#endif
-#if defined(FZ_TS) && FZ_TS == 2
-#define FZ_STAMP2() FZ_STAMP()
-#else
-#define FZ_STAMP2() do { } while (0)
-#endif
-#if defined(FZ_TS) && FZ_TS == 3
-#define FZ_STAMP3() FZ_STAMP()
-#else
-#define FZ_STAMP3() do { } while (0)
-#endif
 
 template <bool COL, bool HAS_T, bool HAS_P = true>
 __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
@@ -83,9 +47,9 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
     const int sstride = NP * NP * 4;                         // bytes per channel of a channel-major image
     const int zstride = COL ? N * 512 : 512;                 // bytes between consecutive pairs of a tile
     auto issue = [&](int s, int buf) {
-#if FZ_ASYM
         // the whole stage is requested by waves 4..7 (8 pieces each): their SIMD partners 0..3 start the stage's MFMAs at once, and the
         // two waves of a SIMD stay half a phase apart for the rest of the stage -- one's VALU phases sit beside the other's MFMAs
+        // (+0.5 % on the step against four pieces from every wave)
         if (wave >= 4) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
@@ -93,13 +57,6 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                 hx_dma(rw, smb + buf * HX_STAGE_BYTES + p * 1024, lane16, s * HX_STAGE_BYTES + p * 1024);
             }
         }
-#else
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int p = 4 * wave + q;
-            hx_dma(rw, smb + buf * HX_STAGE_BYTES + p * 1024, lane16, s * HX_STAGE_BYTES + p * 1024);
-        }
-#endif
     };
     unsigned char* zt = smb + 2 * HX_STAGE_BYTES + 6144 + wave * HX_ZT_BYTES;
     // wave-tile 8 tile + wave (clamped): z byte offset of its first row, valid rows, channel-major element offset of (channel 0, pair 0)
@@ -121,19 +78,7 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
         raw[2 * (c) + 1].z = hx_load(rx, vx, (xoff) + (16 * (c) + 10) * sstride); raw[2 * (c) + 1].w = hx_load(rx, vx, (xoff) + (16 * (c) + 11) * sstride); \
     } while (0)
 
-    // one dword of the same image: element j (0..7) of chunk c
-    auto xld1 = [&](float4 (&raw)[16], int c, int j, int xoff) {
-        const float t = hx_load(rx, vx, xoff + (16 * c + 8 * (j >> 2) + (j & 3)) * sstride);
-        float4& d = raw[2 * c + (j >> 2)];
-        if ((j & 3) == 0) d.x = t; else if ((j & 3) == 1) d.y = t; else if ((j & 3) == 2) d.z = t; else d.w = t;
-    };
     int tile = blockIdx.x;
-    FZ_TS_DECL();
-    if (A.stagger > 0) {        // work-groups start out of phase (experiment: GENIE_FZ_STAGGER = cycles between the first and the last group of eight)
-        const long long t0 = (long long)__builtin_amdgcn_s_memtime();
-        const long long wait = (long long)A.stagger * ((blockIdx.x >> 3) & 7) / 8;
-        while ((long long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-    }
     issue(0, 0);
     for (int u = threadIdx.x; u < FZ_SB_FLOATS; u += 512) {
         float v = 0.f;
@@ -145,16 +90,12 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
         sb[u] = v;
     }
     // Input prefetch, one tile ahead: the first channel half of a tile's z rows (staging area, requested behind projection passes
-    // 4 and 5) and, in chain B, the first half of its x (chunks 0..3, 32 registers, one dword behind each MFMA group of the last four
-    // transition stages -- the one phase without memory traffic of its own).  The rest is requested at the tile's start.
+    // 4 and 5).  x is requested at the tile's start: holding half of the next tile's x (32 registers) through the projections cost
+    // more in spills than the load it hid (chain B 0.877 vs 0.848 ms).
     float4 raw[16];
     {
         int zs, nv, cm;
         tile_geom(tile, zs, nv, cm);
-        if (HAS_T && FZ_XPRE) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) FZ_XLOAD(c, cm);
-        }
         hx_zt_dma(rz, zt, lane, zs, zstride, nv, 1);
     }
     hx_stage_landed();
@@ -178,31 +119,14 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
         int lane_t = lane;                                    // likewise for the ~40 swizzled staging addresses derived from the lane id
         asm volatile("" : "+v"(lane_t));
         const int pl_t = lane_t & 31, h_t = lane_t >> 5;
-        // the rest of the tile's x (chunks 4..7: their lines were touched into L2 by the previous tile, fz_touch_next)
-        FZ_STAMP();
+        // the tile's x
 #pragma unroll
-        for (int c = (HAS_T && FZ_XPRE) ? 4 : 0; c < 8; ++c) FZ_XLOAD(c, cmoff);      // (chain A: all of x here -- no phase of it has room to fetch ahead)
-#if FZ_ZEARLY
-        // z: its second channel half (prefetched by the previous tile) moves from the staging area to registers now, and the first half is
-        // requested right behind the x loads: it lands under the LayerNorm of x and the first stage instead of being waited for at that
-        // stage's end
-        float4 rz1[8];                                        // chunks 4..7
-#pragma unroll
-        for (int q = 0; q < 4; ++q) fz_zt_chunk(rz1[2 * q], rz1[2 * q + 1], zt, pl_t, h_t, q);
-        hx_lds_done();
-        hx_zt_dma(rz, zt, lane_t, zsoff, zstride, znv, 0);
-#endif
+        for (int c = 0; c < 8; ++c) FZ_XLOAD(c, cmoff);
         const float msk = (pl < nvalid) ? A.rmask[b * N + line] * A.rmask[b * N + t0i + pl] : 0.f;
         const bool more = tile + (int)gridDim.x < n_tiles;
         int n_zsoff = 0, n_nv = 1, n_cmoff = 0;
         if (more) tile_geom(tile + gridDim.x, n_zsoff, n_nv, n_cmoff);
-#if FZ_ZEARLY
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // x has landed: at most the 8 z pieces (and the mask loads) are younger
-        __builtin_amdgcn_sched_barrier(0);
-#else
         hx_vm_done();
-#endif
-        FZ_STAMP();
         f32x16 v[4];                                          // the tile's running value: update -> z' -> (z'' accumulators) -> z''
 
         // ------------------------------------------------------------------ O: z' = z + (W_z LN(x) + b_z) sigmoid(W_g LN(z) + b_g)
@@ -210,13 +134,10 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
             h8 xh[8], xl[8];
             hx_norm_split(xh, xl, raw, A.sx);                 // (raw = x; dead from here on)
             PIPE_FENCE();
-            FZ_STAMP3();
             // z: its second channel half (prefetched by the previous tile) goes to registers, its first half is then fetched into the
             // staging area and STAYS there until the gates are done -- chunks of it are read where they are used (32 live registers
             // instead of 64 through the tightest stages).
-#if !FZ_ZEARLY
             float4 rz1[8];                                    // chunks 4..7
-#endif
             float zsh = 0.f, zs1 = 0.f, zs2 = 0.f;            // shifted sums for the LayerNorm statistics
 #pragma unroll
             for (int half = 0; half < 2; ++half) {            // stages 0, 1: update accumulators of channel blocks 2 half, 2 half + 1
@@ -239,13 +160,11 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                     MFH3(f1, f1l, xh[kc], xl[kc], v[2 * half + 1]);
                     PIPE_FENCE();
                     f0 = n0; f0l = n0l; f1 = n1; f1l = n1l;
-#if !FZ_ZEARLY
                     if (half == 0 && kc == 0) {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) fz_zt_chunk(rz1[2 * q], rz1[2 * q + 1], zt, pl_t, h_t, q);
                     }
                     if (half == 0 && kc == 2) { hx_lds_done(); hx_zt_dma(rz, zt, lane_t, zsoff, zstride, znv, 0); }   // first channel half of z
-#endif
                     // LayerNorm statistics of z between this stage's MFMAs, as sums shifted by the row's first element
                     if (half == 1 && kc == 1) {
                         zsh = __shfl(rz1[0].x, lane & 31);         // (the same shift in both half-waves of a row)
@@ -266,13 +185,11 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                 }
                 hx_stage_landed();
                 hx_stage_barrier();
-                FZ_STAMP();
             }
             zs1 += __shfl_xor(zs1, 32); zs2 += __shfl_xor(zs2, 32);
             const float zm_s = zs1 * (1.0f / 128.0f);                                  // mean - shift
             const float zmean = zsh + zm_s;
             const float zsc = A.sx / sqrtf(fmaxf(zs2 * (1.0f / 128.0f) - zm_s * zm_s, 0.f) + GENIE_LN_EPS);
-            FZ_STAMP3();
 #pragma unroll
             for (int half = 0; half < 2; ++half) {            // stages 2, 3: gates of channel blocks 2 half, 2 half + 1, then z'
                 if (half == 0) issue(3, 1);
@@ -324,7 +241,6 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                 }
                 hx_stage_landed();
                 hx_stage_barrier();
-                FZ_STAMP();
             }
         }
 
@@ -338,39 +254,26 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
             for (int ob = 0; ob < 4; ++ob)                    // the residual and b2 are the accumulators' initial value (1 / c2 is a power of two)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[ob][r] = fmaf(v[ob][r], A.inv_c2, sbt[FZ_SB_B2 + ob * 32 + acc_row(r, lane)]);
-#if FZ_BIASPRE
             f32x16 d;
 #pragma unroll
             for (int r = 0; r < 16; ++r) d[r] = sbt[FZ_SB_B1 + acc_row(r, lane)];
-#endif
-            // one hidden block; XC >= 0: the stage also requests chunk XC of the next tile's x, one dword behind each MFMA group of its
-            // first GEMM (the transition has no memory traffic of its own; a burst at a stage's end would not be overlapped)
-            auto t_stage = [&](int hb, auto xc_tag) {
-                constexpr int XC = decltype(xc_tag)::value;
-                if ((FZ_KO & 8) && hb + 1 < n_hb) { }
-                else if (HAS_P || hb + 1 < n_hb) issue(4 + hb + 1, (hb + 1) & 1);     // (hb = n_hb - 1: the first projection stage ...
+            // one hidden block
+            auto t_stage = [&](int hb) {
+                if (HAS_P || hb + 1 < n_hb) issue(4 + hb + 1, (hb + 1) & 1);     // (hb = n_hb - 1: the first projection stage ...
                 else if (more) issue(0, 0);                                      //  ... or, in the chain without projections, the next tile's first stage)
                 const unsigned char* stage = smb + (hb & 1) * HX_STAGE_BYTES;
-#if !FZ_BIASPRE
-                f32x16 d;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) d[r] = sbt[FZ_SB_B1 + hb * 32 + acc_row(r, lane)];
-#endif
                 {
                     h8 wh = hx_frag(stage, 0, 0, lane), wl = hx_frag(stage, 0, 1, lane);
 #pragma unroll
                     for (int kc = 0; kc < 8; ++kc) {
-                        const h8 nh = (FZ_KO & 2) ? wh : hx_frag(stage, min(kc + 1, 7), 0, lane), nl = (FZ_KO & 2) ? wl : hx_frag(stage, min(kc + 1, 7), 1, lane);
+                        const h8 nh = hx_frag(stage, min(kc + 1, 7), 0, lane), nl = hx_frag(stage, min(kc + 1, 7), 1, lane);
                         PIPE_FENCE();
                         MFH3(wh, wl, zh[kc], zl[kc], d);
                         PIPE_FENCE();
                         wh = nh; wl = nl;
-                        if (FZ_XPRE && XC >= 0 && more) xld1(raw, XC < 0 ? 0 : XC, kc, n_cmoff);
                     }
                 }
                 h8 ah[2], al[2];
-                if (FZ_KO & 1) { ah[0] = zh[0]; al[0] = zl[0]; ah[1] = zh[1]; al[1] = zl[1]; }
-                else
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     float x[8];
@@ -382,36 +285,22 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                     h8 bh = hx_frag(stage, 8, 0, lane), bl = hx_frag(stage, 8, 1, lane);
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
-                        const h8 nh = (FZ_KO & 2) ? bh : hx_frag(stage, 8 + min(u + 1, 7), 0, lane), nl = (FZ_KO & 2) ? bl : hx_frag(stage, 8 + min(u + 1, 7), 1, lane);
+                        const h8 nh = hx_frag(stage, 8 + min(u + 1, 7), 0, lane), nl = hx_frag(stage, 8 + min(u + 1, 7), 1, lane);
                         PIPE_FENCE();
                         MFH3(bh, bl, ah[u >> 2], al[u >> 2], v[u & 3]);
                         PIPE_FENCE();
                         bh = nh; bl = nl;
-#if FZ_BIASPRE
                         if (u == 1) {       // d is dead since the split: the next hidden block's biases (block n_hb reads the b2 slots: unused)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) d[r] = sbt[FZ_SB_B1 + (hb + 1) * 32 + acc_row(r, lane)];
                         }
-#endif
                     }
                 }
-                if (FZ_XPRE && XC >= 0 && more) {
-                    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");        // everything older than this stage's 8 x loads: the next stage's weights
-                    __builtin_amdgcn_sched_barrier(0);
-                } else if (!((FZ_KO & 4) && hb + 1 < n_hb))
-                    hx_stage_landed();
-                if (!((FZ_KO & 4) && hb + 1 < n_hb)) hx_stage_barrier();
+                hx_stage_landed();
+                hx_stage_barrier();
             };
-            const int n_plain = (FZ_XPRE && n_hb >= 4) ? n_hb - 4 : n_hb;
 #pragma unroll 1
-            for (int hb = 0; hb < n_plain; ++hb) t_stage(hb, std::integral_constant<int, -1>{});
-            if (FZ_XPRE && n_hb >= 4) {
-                t_stage(n_hb - 4, std::integral_constant<int, 0>{});
-                t_stage(n_hb - 3, std::integral_constant<int, 1>{});
-                t_stage(n_hb - 2, std::integral_constant<int, 2>{});
-                t_stage(n_hb - 1, std::integral_constant<int, 3>{});
-            }
-            FZ_STAMP();
+            for (int hb = 0; hb < n_hb; ++hb) t_stage(hb);
             const float m2 = msk * A.c2;
 #pragma unroll
             for (int ob = 0; ob < 4; ++ob)
@@ -421,18 +310,15 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
 
         // ------------------------------------------------------------------ z leaves (its only write), LayerNorm for the projections
         fz_store_half(rz, zt, v[0], v[1], lane_t, zsoff, zstride, nvalid, 0);
-        FZ_FULL_WAIT(128);
-        FZ_STAMP3();
+        FZ_COMPILER_FENCE();
         fz_store_half(rz, zt, v[2], v[3], lane_t, zsoff, zstride, nvalid, 1);
-        FZ_FULL_WAIT(64);
-        FZ_STAMP3();
+        FZ_COMPILER_FENCE();
         if constexpr (HAS_P) {
             float mean, sc;
             fz_stats(v, A.sx, mean, sc);
             fz_split_tile(zh, zl, v, mean, sc);
         }
         hx_lds_done();                                        // the staging area is free for the next tile's z
-        FZ_STAMP();
         if constexpr (!HAS_P) {                               // (last block: no projections follow; the next tile's z half is requested here)
             if (more) hx_zt_dma(rz, zt, lane_t, n_zsoff, zstride, n_nv, 1);
         }
@@ -459,14 +345,11 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                     const int e_so = sbase + ((pass - 1) & 3) * 32 * sstride;
                     const float e_pm = pp > 2 ? mb : ma;
                     HX_PROJ_STAGE(apA, agA, apB, agB);
-                    FZ_STAMP2();
-                    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                    FZ_STAMP2();      // the next stage's weights (and what was requested a stage ago) have landed
+                    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");      // the next stage's weights (and what was requested a stage ago) have landed
                     if (more) {                                // next tile: x chunks 0..3 behind passes 4, 5; z half 0 behind passes 6, 7
                         if (pp == 2) hx_zt_dma(rz, zt, lane_t, n_zsoff, zstride, n_nv, 1, 0, 4);
                     }
                     hx_stage_barrier();
-                    FZ_STAMP();
                 }
                 {   // odd pass 2pp + 1 -> set B; epilogue of pass 2pp (set A)
                     const int pass = 2 * pp + 1;
@@ -478,14 +361,11 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
                     const int e_so = sbase + ((pass - 1) & 3) * 32 * sstride;
                     const float e_pm = pp < 2 ? ma : mb;
                     HX_PROJ_STAGE(apB, agB, apA, agA);
-                    FZ_STAMP2();
                     asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-                    FZ_STAMP2();
                     if (more) {
                         if (pp == 2) hx_zt_dma(rz, zt, lane_t, n_zsoff, zstride, n_nv, 1, 4, 4);
                     }
                     hx_stage_barrier();
-                    FZ_STAMP();
                 }
             }
             {   // drain: epilogue of pass 7 (set B)
@@ -502,7 +382,6 @@ __global__ __launch_bounds__(512, 1) void k_pair_fused(const FusedArgs A) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) HX_PROJ_PIECE_C_NOW(r, t[r], u[r]);
             }
-            FZ_STAMP();
         }
     }
 #undef FZ_XLOAD
@@ -538,7 +417,6 @@ void launch_pair_fused(genie_ctx* h, hipStream_t st, const HxFusedW& f, const Hx
     a.c1 = t ? t->c1 : 0.f; a.c2 = t ? t->c2 : 1.f; a.inv_c2 = t ? 1.0f / t->c2 : 1.f;
     a.cpa = p.cpa; a.cpb = p.cpb; a.cg = p.cg;
     a.rev = (int)(h->hx_launches++ & 1);
-    { static const int stagger = [] { const char* e = getenv("GENIE_FZ_STAGGER"); return e ? atoi(e) : 0; }(); a.stagger = stagger; }      // developer knob, read once
     const long long n_tiles = ((long long)a.n_wtiles + 7) / 8;
     const unsigned grid = (unsigned)(n_tiles < fz_num_cu() ? n_tiles : fz_num_cu());
     if (!pp) hipLaunchKernelGGL((k_pair_fused<false, true, false>), dim3(grid), dim3(512), FZ_LDS_BYTES, st, a);

@@ -47,7 +47,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_pair_transition_hx
     const bool prefetch = n_hb >= 2;
     const int hq0 = max(0, n_hb / 2 - 2), hq1 = min(n_hb - 1, hq0 + 4);
     int tile = blockIdx.x;
-    HX_TS_DECL(2);
     issue(0, 0);
     for (int u = threadIdx.x; u < n_hb * 32; u += NW * 64) sb1[u] = b1s[u];
     const float cb0 = b2s[pl], cb1 = b2s[32 + pl], cb2 = b2s[64 + pl], cb3 = b2s[96 + pl];
@@ -89,19 +88,16 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_pair_transition_hx
         const int srow0 = (int)(row0 * 512);
         auto stage_body = [&](int hb, auto last_tag) {
             constexpr bool LAST = decltype(last_tag)::value;
-            HX_TS();
             if (more && prefetch) {
                 if (hb == hq0) { tile_geom(tile + gridDim.x, n_soff, n_nv); hx_zt_dma(rz, zt, lane, n_soff, 512, n_nv, 0); }
                 if (hb == hq1) { hx_zt_read(raw, zt, pl, h, 0); hx_lds_done(); hx_zt_dma(rz, zt, lane, n_soff, 512, n_nv, 1); }
             }
             if (!LAST) issue(hb + 1, (hb + 1) & 1);
             else if (more) issue(0, 0);
-            HX_TS2();
             const unsigned char* stage = smb + (hb & 1) * HX_STAGE_BYTES;
             f32x16 d;
 #pragma unroll
             for (int r = 0; r < 16; ++r) d[r] = sb1[hb * 32 + acc_row(r, lane)];
-            HX_TS2();
             {
                 h8 wh = hx_frag(stage, 0, 0, lane), wl = hx_frag(stage, 0, 1, lane);
 #pragma unroll
@@ -110,11 +106,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_pair_transition_hx
                     PIPE_FENCE();
                     MFH3(wh, wl, zh[kc], zl[kc], d);
                     PIPE_FENCE();
-                    if (kc == 0 || kc == 3) HX_TS2();
                     wh = nh; wl = nl;
                 }
             }
-            HX_TS();
             if (LAST) {     // zh / zl are dead from here on: the first half of the residual rows is fetched while the last GEMM runs
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
@@ -142,9 +136,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_pair_transition_hx
                     bh = nh; bl = nl;
                 }
             }
-            HX_TS();
             __syncthreads();
-            HX_TS();
         };
 #pragma unroll 1
         for (int hb = 0; hb + 1 < n_hb; ++hb) stage_body(hb, std::false_type{});
@@ -215,7 +207,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_proj_hx(
         soff = OUTGOING ? ((b * N + line) * N + st * 32) * 512 : ((b * N + st * 32) * N + line) * 512;
     };
     int tile = blockIdx.x;
-    HX_TS_DECL(OUTGOING ? 1 : 0);
     issue(0, 0);
     for (int u = threadIdx.x; u < 512; u += NW * 64) sbias[u] = bias[u];
     __syncthreads();
@@ -245,13 +236,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_proj_hx(
         const int voff = (pl < nvalid) ? (4 * h * NP * NP + pl) * 4 : 0x7FFFFFF0;   // out-of-range offset: store dropped
         const int sbase = ((b * 128 * NP + line) * NP + t0i) * 4;
         const bool more = tile + (int)gridDim.x < n_tiles;
-        HX_TS();
         hx_norm_split(zh, zl, raw, sx);
 #pragma unroll 1
         for (int pp = 0; pp < 4; ++pp) {
             {   // even pass 2pp -> set A; epilogue of pass 2pp - 1 (set B; for pp = 0 the previous tile's pass 7)
                 const int pass = 2 * pp;
-                HX_TS();
                 if (more) {                               // next tile's rows: first half -> raw at pass 4 (requested at the ends of passes 0..2)
                     if (pp == 0) tile_geom(tile + gridDim.x, n_soff, n_nv);
                     if (pp == 2) { hx_zt_read(raw, zt, pl, h, 0); hx_lds_done(); }
@@ -263,7 +252,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_proj_hx(
                 const int e_so = pp == 0 ? p_so : sbase + ((pass - 1) & 3) * 32 * sstride;
                 const float e_pm = pp == 0 ? p_pm : (pp > 2 ? mb : ma);
                 HX_PROJ_STAGE(apA, agA, apB, agB);
-                HX_TS();
                 asm volatile("s_waitcnt vmcnt(16)" ::: "memory");      // weights of the next stage + the row-tile pieces requested a stage ago
                 if (more) {                               // row-tile requests AFTER the stage's last store: passes 0, 2 -> half 0; 4, 6 -> half 1
                     if (pp == 0) hx_zt_dma(rz, zt, lane, n_soff, zstride, n_nv, 0, 0, 3);
@@ -271,12 +259,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_proj_hx(
                     else if (pp == 2) hx_zt_dma(rz, zt, lane, n_soff, zstride, n_nv, 1, 0, 3);
                     else hx_zt_dma(rz, zt, lane, n_soff, zstride, n_nv, 1, 6, 2);
                 }
-                HX_TS(); hx_stage_barrier();
-                HX_TS();
+                hx_stage_barrier();
             }
             {   // odd pass 2pp + 1 -> set B; epilogue of pass 2pp (set A)
                 const int pass = 2 * pp + 1;
-                HX_TS();
                 if (pp < 3) issue(pass + 1, 0);
                 else if (more) issue(0, 0);
                 const unsigned char* stage = smb + HX_STAGE_BYTES;
@@ -285,14 +271,12 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_proj_hx(
                 const int e_so = sbase + ((pass - 1) & 3) * 32 * sstride;
                 const float e_pm = pp < 2 ? ma : mb;
                 HX_PROJ_STAGE(apB, agB, apA, agA);
-                HX_TS();
                 asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
                 if (more) {                               // passes 1 -> half 0, 5 -> half 1 (none after passes 3 and 7: the halves are read next)
                     if (pp == 0) hx_zt_dma(rz, zt, lane, n_soff, zstride, n_nv, 0, 3, 3);
                     else if (pp == 2) hx_zt_dma(rz, zt, lane, n_soff, zstride, n_nv, 1, 3, 3);
                 }
-                HX_TS(); hx_stage_barrier();
-                HX_TS();
+                hx_stage_barrier();
             }
         }
         p_voff = voff; p_so = sbase + 3 * 32 * sstride; p_pm = mb;
@@ -549,9 +533,6 @@ __global__ __launch_bounds__(512, 1) void k_trimul_contract_hx_big(const unsigne
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const float v = acc[m][n][r] * cx;
-#if HX_ABL & 512      // developer knock-out (timing only): one store in sixteen
-                            if (r == 0)
-#endif
                             hx_store(rx, v, vst, sbase + ((r & 3) + 8 * (r >> 2)) * NP * 4);
                         }
                     }
@@ -575,163 +556,10 @@ __global__ __launch_bounds__(512, 1) void k_trimul_contract_hx_big(const unsigne
 // A operand = the pair tile (zn, then xn), B = weights; stages W_g{0,1}, W_z{0,1}, W_g{2,3}, W_z{2,3},
 // unit = 8 (output block within the stage) + k-chunk.  x arrives channel-major: lane (p, h) reads
 // x[c][p] for its 64 channels c = 16kc + 8h + e (each load = two 128-B runs).
+// All four weight stages stay resident in LDS (128 KiB: no weight stream, no barrier inside the tile loop -- the eight waves of a
+// work-group run their tiles independently), and the z rows are loaded straight into operand registers (no LDS is left for a
+// row-tile loader).  Against the same kernel with the weights streamed through two LDS stages: 0.233 vs 0.240 ms per launch.
 // ---------------------------------------------------------------------------------------------
-template <int NW>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_out_hx(
-    float* __restrict__ z, const float* __restrict__ xcm, const unsigned char* __restrict__ wimg,
-    const float* __restrict__ bgs, const float* __restrict__ bzs, int N, int NP, int n_wtiles, unsigned cm_bytes,
-    unsigned z_bytes, float sx, float cg, float cz, int rev) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
-    const int lane = threadIdx.x & 63, wave = UNI(threadIdx.x >> 6);
-    const int h = lane >> 5, pl = lane & 31;
-    const int ntile = (N + 31) >> 5;
-    const int n_tiles = (n_wtiles + NW - 1) / NW;
-    const rsrc_t rw = hx_rsrc(wimg, 4 * HX_STAGE_BYTES);
-    const rsrc_t rx = hx_rsrc(xcm, cm_bytes), rz = hx_rsrc(z, z_bytes);
-    const int lane16 = lane * 16;
-    constexpr int PW = 32 / NW;
-    auto issue = [&](int s, int buf) {
-#pragma unroll
-        for (int q = 0; q < PW; ++q) {
-            const int p = PW * wave + q;
-            hx_dma(rw, smb + buf * HX_STAGE_BYTES + p * 1024, lane16, s * HX_STAGE_BYTES + p * 1024);
-        }
-    };
-    unsigned char* zt = smb + 2 * HX_STAGE_BYTES + 2048 + wave * HX_ZT_BYTES;
-    int tile = blockIdx.x;
-    issue(0, 0);
-    __syncthreads();
-#pragma unroll 1
-    for (; tile < n_tiles; tile += gridDim.x) {
-        const int wt_raw = HX_PHYS(tile) * NW + wave;
-        const bool act = wt_raw < n_wtiles;
-        const int wt = act ? wt_raw : n_wtiles - 1;
-        const int st = wt % ntile, i = (wt / ntile) % N, b = wt / (ntile * N);
-        const int t0 = st * 32;
-        const int nvalid = act ? min(32, N - t0) : 0;
-        const int prow0 = (b * N + i) * N + t0;                  // first pair row of the tile
-        const bool more = tile + (int)gridDim.x < n_tiles;
-        h8 zh[8], zl[8], xh[8], xl[8];
-        {   // x_cm[((b*128 + c)*NP + i)*NP + t0 + pl], c = 16kc + 8h + e   (t0 + pl < NP always); the z rows come through the
-            // coalesced LDS loader (two halves), the second half's latency is spent on LayerNorm + split of x
-            float4 raw[16], rawz[16];
-            const int cs = NP * NP * 4;
-            const int vx = (8 * h * NP * NP + pl) * 4;
-            const int sxo = ((b * 128 * NP + i) * NP + t0) * 4;
-#pragma unroll
-            for (int kc = 0; kc < 8; ++kc) {
-                raw[2 * kc].x = hx_load(rx, vx, sxo + (16 * kc + 0) * cs); raw[2 * kc].y = hx_load(rx, vx, sxo + (16 * kc + 1) * cs);
-                raw[2 * kc].z = hx_load(rx, vx, sxo + (16 * kc + 2) * cs); raw[2 * kc].w = hx_load(rx, vx, sxo + (16 * kc + 3) * cs);
-                raw[2 * kc + 1].x = hx_load(rx, vx, sxo + (16 * kc + 4) * cs); raw[2 * kc + 1].y = hx_load(rx, vx, sxo + (16 * kc + 5) * cs);
-                raw[2 * kc + 1].z = hx_load(rx, vx, sxo + (16 * kc + 6) * cs); raw[2 * kc + 1].w = hx_load(rx, vx, sxo + (16 * kc + 7) * cs);
-            }
-            const int zsoff = prow0 * 512, znv = min(32, N - t0);
-            hx_zt_dma(rz, zt, lane, zsoff, 512, znv, 0); hx_vm_done(); hx_zt_read(rawz, zt, pl, h, 0); hx_lds_done();
-            hx_zt_dma(rz, zt, lane, zsoff, 512, znv, 1);
-            hx_norm_split(xh, xl, raw, sx);
-            hx_vm_done(); hx_zt_read(rawz, zt, pl, h, 1);
-            hx_norm_split(zh, zl, rawz, sx);
-        }
-        const int voff = (4 * h * 128 + pl) * 4;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            f32x16 ga, gb;
-            {   // gate: A = zn fragments (i = pair), B = W_g (j = channel)
-                issue(2 * half + 1, 1);
-                const unsigned char* stage = smb;
-                float c0 = bgs[(2 * half) * 32 + pl], c1 = bgs[(2 * half + 1) * 32 + pl];
-                asm volatile("" : "+v"(c0), "+v"(c1));      // keep hipcc from hoisting (and spilling) the 16-register splats
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { ga[r] = c0; gb[r] = c1; }
-                h8 f0 = hx_frag(stage, 0, 0, lane), f0l = hx_frag(stage, 0, 1, lane), f1 = hx_frag(stage, 8, 0, lane),
-                   f1l = hx_frag(stage, 8, 1, lane);
-#pragma unroll
-                for (int kc = 0; kc < 8; ++kc) {
-                    const int kn = min(kc + 1, 7);
-                    const h8 n0 = hx_frag(stage, kn, 0, lane), n0l = hx_frag(stage, kn, 1, lane), n1 = hx_frag(stage, 8 + kn, 0, lane),
-                             n1l = hx_frag(stage, 8 + kn, 1, lane);
-                    PIPE_FENCE();
-                    MFH3(zh[kc], zl[kc], f0, f0l, ga);
-                    MFH3(zh[kc], zl[kc], f1, f1l, gb);
-                    PIPE_FENCE();
-                    f0 = n0; f0l = n0l; f1 = n1; f1l = n1l;
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    ga[r] = cz * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(ga[r] * cg));
-                    gb[r] = cz * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gb[r] * cg));
-                }
-                __syncthreads();
-            }
-            {   // update of channel blocks 2 half, 2 half + 1
-                if (half == 0) issue(2, 0);
-                else if (more) issue(0, 0);
-                const unsigned char* stage = smb + HX_STAGE_BYTES;
-                const int ob = 2 * half;
-                f32x16 a0, a1;
-                float c0 = bzs[ob * 32 + pl], c1 = bzs[(ob + 1) * 32 + pl];
-                asm volatile("" : "+v"(c0), "+v"(c1));
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { a0[r] = c0; a1[r] = c1; }
-                const int h4 = 4 * h;
-                float zp0[16], zp1[16];
-                if (half == 1) {    // zh / zl are dead after the second gate: the residual rows of this half are requested before its GEMM
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rc = (r & 3) + 8 * (r >> 2);
-                        const int so = (prow0 + rc) * 512 + ob * 128;
-                        const int vr = (h4 < nvalid - rc) ? voff : 0x7FFFFFF0;
-                        zp0[r] = hx_load(rz, vr, so);
-                        zp1[r] = hx_load(rz, vr, so + 128);
-                    }
-                }
-                h8 f0 = hx_frag(stage, 0, 0, lane), f0l = hx_frag(stage, 0, 1, lane), f1 = hx_frag(stage, 8, 0, lane),
-                   f1l = hx_frag(stage, 8, 1, lane);
-#pragma unroll
-                for (int kc = 0; kc < 8; ++kc) {
-                    const int kn = min(kc + 1, 7);
-                    const h8 n0 = hx_frag(stage, kn, 0, lane), n0l = hx_frag(stage, kn, 1, lane), n1 = hx_frag(stage, 8 + kn, 0, lane),
-                             n1l = hx_frag(stage, 8 + kn, 1, lane);
-                    PIPE_FENCE();
-                    MFH3(xh[kc], xl[kc], f0, f0l, a0);
-                    MFH3(xh[kc], xl[kc], f1, f1l, a1);
-                    PIPE_FENCE();
-                    f0 = n0; f0l = n0l; f1 = n1; f1l = n1l;
-                }
-                hx_stage_landed();
-                // residual + store, 8 rows (16 loads) in flight at a time; rows past the tile's valid pairs belong to
-                // the next line: their offset is pushed out of the buffer (load gives 0, store is dropped)
-#pragma unroll
-                for (int r0 = 0; r0 < 16; r0 += 8) {
-                    float zr0[8], zr1[8];
-                    int vo[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int rc = ((r0 + q) & 3) + 8 * ((r0 + q) >> 2);
-                        const int so = (prow0 + rc) * 512 + ob * 128;
-                        vo[q] = (h4 < nvalid - rc) ? voff : 0x7FFFFFF0;
-                        if (half == 1) { zr0[q] = zp0[r0 + q]; zr1[q] = zp1[r0 + q]; }
-                        else { zr0[q] = hx_load(rz, vo[q], so); zr1[q] = hx_load(rz, vo[q], so + 128); }
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int rc = ((r0 + q) & 3) + 8 * ((r0 + q) >> 2);
-                        const int so = (prow0 + rc) * 512 + ob * 128;
-                        const float u0 = a0[r0 + q], u1 = a1[r0 + q], g0 = ga[r0 + q], g1 = gb[r0 + q];
-                        hx_store(rz, fmaf(u0, g0, zr0[q]), vo[q], so);
-                        hx_store(rz, fmaf(u1, g1, zr1[q]), vo[q], so + 128);
-                    }
-                    PIPE_FENCE();
-                }
-                hx_stage_barrier();
-            }
-        }
-    }
-}
-
-// The same kernel with all four weight stages resident in LDS (128 KiB: no weight stream, no barrier inside the tile loop --
-// the eight waves of a work-group run their tiles independently) and the z rows loaded straight into operand registers
-// (no LDS left for the row-tile loader).
 template <int NW>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_out_hx_r(
     float* __restrict__ z, const float* __restrict__ xcm, const unsigned char* __restrict__ wimg,
@@ -767,8 +595,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void k_trimul_out_hx_r(
         const int nvalid = act ? min(32, N - t0) : 0;
         const int prow0 = (b * N + i) * N + t0;                  // first pair row of the tile
         h8 zh[8], zl[8], xh[8], xl[8];
-        {   // x_cm[((b*128 + c)*NP + i)*NP + t0 + pl], c = 16kc + 8h + e   (t0 + pl < NP always); the z rows come through the
-            // coalesced LDS loader (two halves), the second half's latency is spent on LayerNorm + split of x
+        {   // x_cm[((b*128 + c)*NP + i)*NP + t0 + pl], c = 16kc + 8h + e   (t0 + pl < NP always)
             float4 raw[16], rawz[16];
             const int cs = NP * NP * 4;
             const int vx = (8 * h * NP * NP + pl) * 4;
@@ -895,106 +722,90 @@ static int hx_num_cu() {
     return g_hx_cu;
 }
 static int hx_nw() { return 8; }   // waves per work-group (one work-group per CU: 130 KiB of LDS)
-// `cus`: CUs this launch may fill (all of them, or half when two halves of the batch run side by side)
-static unsigned hx_grid(long long n_tiles, int nw, int cus) {
-    const long long cap = (nw == 8 ? 1LL : 2LL) * cus;
+static unsigned hx_grid(long long n_tiles, int nw) {
+    const long long cap = (nw == 8 ? 1LL : 2LL) * hx_num_cu();
     return (unsigned)(n_tiles < cap ? n_tiles : cap);
 }
 
-// A contiguous slice of the batch (structures b0 .. b0 + nb - 1) on its own stream: every pair-stack kernel is separable over
-// the batch (outermost dimension of p, a, b, x and of the mask), so a slice is a pointer offset and a smaller tile count.
-struct HxSlice { int b0, nb; hipStream_t st; int cus; unsigned launches; bool prof; };
-
-static void pair_transition_slice(genie_ctx* h, HxSlice& v, const PairLayerW& w) {
+// Every pair-stack launch takes the next tile direction: `rev` = parity of h->hx_launches, which it then increments.
+void launch_pair_transition_hx(genie_ctx* h, hipStream_t st, const PairLayerW& w) {
     const int N = h->N;
-    const long long M = (long long)v.nb * N * N;
+    const long long M = (long long)h->B * N * N;
     const long long n_wt = (M + 31) / 32;
     const int n_hb = h->d.pair_transition_n * 4;
     const HxTransW& x = w.hx_pt;
-    hipLaunchKernelGGL(k_pair_transition_hx<8>, dim3(hx_grid((n_wt + 7) / 8, 8, v.cus)), dim3(512), HX_LDS_BYTES, v.st,
-                       h->p + (size_t)v.b0 * N * N * 128, h->rmaskf + (size_t)v.b0 * N, x.img, x.b1s, x.b2s, N, M, n_hb, x.sx, x.c1, x.c2,
-                       (int)(v.launches++ & 1));
+    hipLaunchKernelGGL(k_pair_transition_hx<8>, dim3(hx_grid((n_wt + 7) / 8, 8)), dim3(512), HX_LDS_BYTES, st, h->p, h->rmaskf, x.img,
+                       x.b1s, x.b2s, N, M, n_hb, x.sx, x.c1, x.c2, (int)(h->hx_launches++ & 1));
 }
 
 struct HxTriGeom {
     int N, NP, ntile, nw, n_wt;
-    unsigned *acm, *bcm; float* xcm; float* zs; const float* ms;
     unsigned cm_bytes, z_bytes;
 };
-static HxTriGeom tri_geom(genie_ctx* h, const HxSlice& v) {
+static HxTriGeom tri_geom(const genie_ctx* h) {
     HxTriGeom g;
     g.N = h->N; g.NP = h->NP; g.ntile = (g.N + 31) / 32; g.nw = hx_nw();
-    const size_t cm_off = (size_t)v.b0 * 128 * g.NP * g.NP;
-    g.acm = reinterpret_cast<unsigned*>(h->acm) + cm_off;
-    g.bcm = reinterpret_cast<unsigned*>(h->bcm) + cm_off;
-    g.xcm = h->xcm + cm_off;
-    g.n_wt = v.nb * g.N * g.ntile;
-    g.cm_bytes = (unsigned)((size_t)v.nb * 128 * g.NP * g.NP * 4);
-    g.z_bytes = (unsigned)((size_t)v.nb * g.N * g.N * 512);
-    g.zs = h->p + (size_t)v.b0 * g.N * g.N * 128;
-    g.ms = h->rmaskf + (size_t)v.b0 * g.N;
+    g.n_wt = h->B * g.N * g.ntile;
+    g.cm_bytes = (unsigned)((size_t)h->B * 128 * g.NP * g.NP * 4);
+    g.z_bytes = (unsigned)((size_t)h->B * g.N * g.N * 512);
     return g;
 }
 
-static void trimul_proj_slice(genie_ctx* h, HxSlice& v, const TriMulW& w, bool outgoing) {
-    const HxTriGeom g = tri_geom(h, v);
+static void hx_trimul_proj(genie_ctx* h, hipStream_t st, const TriMulW& w, bool outgoing) {
+    const HxTriGeom g = tri_geom(h);
     const HxTriW& x = w.hx;
-    hipStream_t st = v.st;
-    ProfScope ps(h, st, KC_TRIMUL_PROJ, v.prof);
-    const dim3 grid(hx_grid((g.n_wt + g.nw - 1) / g.nw, g.nw, v.cus)), block(g.nw * 64);
-    const int rev = (int)(v.launches++ & 1);
-#define HX_PROJ(OUT, NWV) hipLaunchKernelGGL((k_trimul_proj_hx<OUT, NWV>), grid, block, HX_LDS_BYTES, st, g.zs, g.ms, x.img_proj, \
-                                         x.bias_proj, g.acm, g.bcm, g.N, g.NP, g.n_wt, g.cm_bytes, g.z_bytes, x.sx, x.cpa, x.cpb, x.cg, rev)
+    unsigned* acm = reinterpret_cast<unsigned*>(h->acm);
+    unsigned* bcm = reinterpret_cast<unsigned*>(h->bcm);
+    ProfScope ps(h, st, KC_TRIMUL_PROJ);
+    const dim3 grid(hx_grid((g.n_wt + g.nw - 1) / g.nw, g.nw)), block(g.nw * 64);
+    const int rev = (int)(h->hx_launches++ & 1);
+#define HX_PROJ(OUT, NWV) hipLaunchKernelGGL((k_trimul_proj_hx<OUT, NWV>), grid, block, HX_LDS_BYTES, st, h->p, h->rmaskf, x.img_proj, \
+                                         x.bias_proj, acm, bcm, g.N, g.NP, g.n_wt, g.cm_bytes, g.z_bytes, x.sx, x.cpa, x.cpb, x.cg, rev)
     if (outgoing) HX_PROJ(true, 8);
     else HX_PROJ(false, 8);
 #undef HX_PROJ
 }
 
 // x = a b^T per channel; `transposed`: the operands swapped, which leaves x^T (what the column-tile chain A reads)
-static void trimul_contract_slice(genie_ctx* h, HxSlice& v, const TriMulW& w, bool transposed) {
-    const HxTriGeom g = tri_geom(h, v);
+static void hx_trimul_contract(genie_ctx* h, hipStream_t st, const TriMulW& w, bool transposed) {
+    const HxTriGeom g = tri_geom(h);
     const HxTriW& x = w.hx;
-    hipStream_t st = v.st;
-    ProfScope ps(h, st, KC_TRIMUL_CONTRACT, v.prof);
-    const int BC = v.nb * h->d.c_hidden_mul;
-    const int ncu = v.cus;
-    const int rev = (int)(v.launches++ & 1);
-    const unsigned* pa = transposed ? g.bcm : g.acm;
-    const unsigned* pb = transposed ? g.acm : g.bcm;
-    if (g.NP > 192 && g.NP <= 256 && !getenv("GENIE_CONTRACT_TILED")) {
-        hipLaunchKernelGGL(k_trimul_contract_hx_big, dim3(BC < ncu ? BC : ncu), dim3(512), 4 * CB_PLANE, st, pa, pb, g.xcm, g.NP, BC, g.cm_bytes,
+    ProfScope ps(h, st, KC_TRIMUL_CONTRACT);
+    const int BC = h->B * h->d.c_hidden_mul;
+    const int ncu = hx_num_cu();
+    const int rev = (int)(h->hx_launches++ & 1);
+    const unsigned* acm = reinterpret_cast<const unsigned*>(h->acm);
+    const unsigned* bcm = reinterpret_cast<const unsigned*>(h->bcm);
+    const unsigned* pa = transposed ? bcm : acm;
+    const unsigned* pb = transposed ? acm : bcm;
+    if (g.NP > 192 && g.NP <= 256) {
+        hipLaunchKernelGGL(k_trimul_contract_hx_big, dim3(BC < ncu ? BC : ncu), dim3(512), 4 * CB_PLANE, st, pa, pb, h->xcm, g.NP, BC, g.cm_bytes,
                            x.cx, rev);
     } else if (g.NP >= 128) {
         const int tiles = (g.NP + 127) / 128;
         const int n_tiles = tiles * tiles * ((BC + 7) / 8) * 8;
         hipLaunchKernelGGL(k_trimul_contract_hx<2>, dim3(n_tiles < 3 * ncu ? n_tiles : 3 * ncu), dim3(256), 2 * 4 * 128 * CX_ROWB, st,
-                           pa, pb, g.xcm, g.NP, BC, g.cm_bytes, x.cx, rev);
+                           pa, pb, h->xcm, g.NP, BC, g.cm_bytes, x.cx, rev);
     } else {
         const int tiles = (g.NP + 63) / 64;
         const int n_tiles = tiles * tiles * ((BC + 7) / 8) * 8;
         hipLaunchKernelGGL(k_trimul_contract_hx<1>, dim3(n_tiles < 4 * ncu ? n_tiles : 4 * ncu), dim3(256), 2 * 4 * 64 * CX_ROWB, st,
-                           pa, pb, g.xcm, g.NP, BC, g.cm_bytes, x.cx, rev);
+                           pa, pb, h->xcm, g.NP, BC, g.cm_bytes, x.cx, rev);
     }
 }
 
-static void trimul_out_slice(genie_ctx* h, HxSlice& v, const TriMulW& w) {
-    const HxTriGeom g = tri_geom(h, v);
+static void hx_trimul_out(genie_ctx* h, hipStream_t st, const TriMulW& w) {
+    const HxTriGeom g = tri_geom(h);
     const HxTriW& x = w.hx;
-    hipStream_t st = v.st;
-    ProfScope ps(h, st, KC_TRIMUL_OUT, v.prof);
-    const bool resident = getenv("GENIE_OUT_STREAMED") == nullptr;     // default: weights resident in LDS (0.233 vs 0.240 ms per launch)
-    if (resident)
-        hipLaunchKernelGGL(k_trimul_out_hx_r<8>, dim3(hx_grid((g.n_wt + 7) / 8, 8, v.cus)), dim3(512), 4 * HX_STAGE_BYTES, st, g.zs, g.xcm,
-                           x.img_out, x.bgs, x.bzs, g.N, g.NP, g.n_wt, g.cm_bytes, g.z_bytes, x.sx, x.cgo, x.cz, (int)(v.launches++ & 1));
-    else
-        hipLaunchKernelGGL(k_trimul_out_hx<8>, dim3(hx_grid((g.n_wt + 7) / 8, 8, v.cus)), dim3(512), HX_LDS_BYTES, st, g.zs, g.xcm, x.img_out,
-                           x.bgs, x.bzs, g.N, g.NP, g.n_wt, g.cm_bytes, g.z_bytes, x.sx, x.cgo, x.cz, (int)(v.launches++ & 1));
+    ProfScope ps(h, st, KC_TRIMUL_OUT);
+    hipLaunchKernelGGL(k_trimul_out_hx_r<8>, dim3(hx_grid((g.n_wt + 7) / 8, 8)), dim3(512), 4 * HX_STAGE_BYTES, st, h->p, h->xcm,
+                       x.img_out, x.bgs, x.bzs, g.N, g.NP, g.n_wt, g.cm_bytes, g.z_bytes, x.sx, x.cgo, x.cz, (int)(h->hx_launches++ & 1));
 }
 
-static void trimul_slice(genie_ctx* h, HxSlice& v, const TriMulW& w, bool outgoing) {
-    trimul_proj_slice(h, v, w, outgoing);
-    trimul_contract_slice(h, v, w, false);
-    trimul_out_slice(h, v, w);
+void launch_trimul_hx(genie_ctx* h, hipStream_t st, const TriMulW& w, bool outgoing) {
+    hx_trimul_proj(h, st, w, outgoing);
+    hx_trimul_contract(h, st, w, false);
+    hx_trimul_out(h, st, w);
 }
 
 // The whole pair transform net with the row-local chains fused (pair_fused_kernels.hip):
@@ -1003,62 +814,30 @@ static void trimul_slice(genie_ctx* h, HxSlice& v, const TriMulW& w, bool outgoi
 void launch_pair_fused(genie_ctx* h, hipStream_t st, const HxFusedW& f, const HxTriW& o, const HxTransW* t, const HxTriW* p, bool col);
 bool launch_pair_stack_fused(genie_ctx* h, hipStream_t st, float* tap_trimul_out0, float* tap_layer0) {
     const int L = h->d.n_pair_transform_layer;
-    if (!h->hx || L < 1 || getenv("GENIE_NO_PAIR_FUSE") || (getenv("GENIE_HX_SLICE") && atoi(getenv("GENIE_HX_SLICE")) > 0)) return false;
-    if ((h->d.pair_transition_n * 4) & 1) return false;
+    if (!h->hx || L < 1 || getenv("GENIE_NO_PAIR_FUSE")) return false;
     const size_t pbytes = (size_t)h->B * h->N * h->N * h->d.c_p * 4;
-    HxSlice v{0, h->B, st, hx_num_cu(), h->hx_launches, h->prof};
-    trimul_proj_slice(h, v, h->pair[0].out, true);
+    hx_trimul_proj(h, st, h->pair[0].out, true);
     for (int l = 0; l < L; ++l) {
         const PairLayerW& W = h->pair[l];
-        trimul_contract_slice(h, v, W.out, true);
-        h->hx_launches = v.launches;
+        hx_trimul_contract(h, st, W.out, true);
         { ProfScope ps(h, st, KC_PAIR_FUSED_A); launch_pair_fused(h, st, W.fa, W.out.hx, nullptr, &W.in.hx, true); }
-        v.launches = h->hx_launches;
         if (l == 0 && tap_trimul_out0) (void)hipMemcpyAsync(tap_trimul_out0, h->p, pbytes, hipMemcpyDeviceToDevice, st);
-        trimul_contract_slice(h, v, W.in, false);
-        if (l + 1 < L) {
-            h->hx_launches = v.launches;
-            { ProfScope ps(h, st, KC_PAIR_FUSED_B); launch_pair_fused(h, st, W.fb, W.in.hx, &W.hx_pt, &h->pair[l + 1].out.hx, false); }
-            v.launches = h->hx_launches;
-        } else {       // last block: the same chain without projections
-            h->hx_launches = v.launches;
-            { ProfScope ps(h, st, KC_PAIR_FUSED_B); launch_pair_fused(h, st, W.fb, W.in.hx, &W.hx_pt, nullptr, false); }
-            v.launches = h->hx_launches;
+        hx_trimul_contract(h, st, W.in, false);
+        {   // (last block: the same chain without projections)
+            ProfScope ps(h, st, KC_PAIR_FUSED_B);
+            launch_pair_fused(h, st, W.fb, W.in.hx, &W.hx_pt, l + 1 < L ? &h->pair[l + 1].out.hx : nullptr, false);
         }
         if (l == 0 && tap_layer0) (void)hipMemcpyAsync(tap_layer0, h->p, pbytes, hipMemcpyDeviceToDevice, st);
     }
-    h->hx_launches = v.launches;
     return true;
 }
 
-void launch_pair_transition_hx(genie_ctx* h, hipStream_t st, const PairLayerW& w) {
-    HxSlice v{0, h->B, st, hx_num_cu(), h->hx_launches, h->prof};
-    pair_transition_slice(h, v, w);
-    h->hx_launches = v.launches;
-}
-
-// GENIE_HX_SLICE=n runs the three kernels of a triangle multiplication per slice of n structures, so that (n = 2, N = 256:
-// a + b + x = 201 MB) the operands stay in the 256-MiB Infinity Cache between producer and consumer.  Measured: no gain
-// (82.1 / 80.4 / 83.0 / 80.9 batch-steps/s for n = 8 / 4 / 2 / 1), so the default is the whole batch; kept as a switch for larger N.
-static int g_hx_slice = 0;
-static int hx_slice() {
-    if (!g_hx_slice) { const char* e = getenv("GENIE_HX_SLICE"); g_hx_slice = e && atoi(e) > 0 ? atoi(e) : 1 << 20; }
-    return g_hx_slice;
-}
-
-void launch_trimul_hx(genie_ctx* h, hipStream_t st, const TriMulW& w, bool outgoing) {
-    const int SB = hx_slice();
-    for (int b0 = 0; b0 < h->B; b0 += SB) {
-        HxSlice v{b0, h->B - b0 < SB ? h->B - b0 : SB, st, hx_num_cu(), h->hx_launches, h->prof};
-        trimul_slice(h, v, w, outgoing);
-        h->hx_launches = v.launches;
-    }
-}
-
-// (Tried on top of the slices: the whole pair transform net with the batch in two halves on two streams, each on half of the
-//  CUs, the second half one or two kernels behind the first, so that a memory-bound TriMul kernel and the matrix-bound
-//  transition run side by side.  89.6 - 94.2 batch-steps/s against 95.1: a kernel on half of the CUs takes twice as long,
-//  whether it is bound by memory or by the matrix pipe.)
+// (Tried: the three kernels of a triangle multiplication per slice of n structures, so that (n = 2, N = 256: a + b + x = 201 MB)
+//  the operands stay in the 256-MiB Infinity Cache between producer and consumer.  No gain: 82.1 / 80.4 / 83.0 / 80.9
+//  batch-steps/s for n = 8 / 4 / 2 / 1.  Also tried: the whole pair transform net with the batch in two halves on two streams, each
+//  on half of the CUs, the second half one or two kernels behind the first, so that a memory-bound TriMul kernel and the
+//  matrix-bound transition run side by side.  89.6 - 94.2 batch-steps/s against 95.1: a kernel on half of the CUs takes twice as
+//  long, whether it is bound by memory or by the matrix pipe.)
 
 // ---------------------------------------------------------------------------------------------
 // Pair bias of all IPA layers in one pass over p (invariant_point_attention.py:181), hx arithmetic:
@@ -1141,7 +920,7 @@ __global__ __launch_bounds__(256) void k_ipa_bias_hx(const float* __restrict__ z
 
 bool launch_ipa_bias_hx(genie_ctx* h, hipStream_t st) {
     const int LH = h->d.n_structure_layer * h->d.n_head_ipa;
-    if (!h->hx || LH > 96 || h->d.c_p != 128 || getenv("GENIE_IPA_BIAS_F32")) return false;
+    if (!h->hx || LH > 96) return false;
     const HxGemmW* w = nullptr;
     for (int i = 0; i < h->n_hxg; ++i)
         if (h->hxg[i].w == h->ipa_bias_w) w = &h->hxg[i];
@@ -1157,7 +936,7 @@ bool launch_ipa_bias_hx(genie_ctx* h, hipStream_t st) {
 void pair_hx_kernels_init() {
 #define HX_ATTR(k) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, HX_LDS_BYTES)
     HX_ATTR((k_trimul_proj_hx<true, 8>)); HX_ATTR((k_trimul_proj_hx<false, 8>));
-    HX_ATTR(k_trimul_out_hx<8>); HX_ATTR(k_trimul_out_hx_r<8>);
+    HX_ATTR(k_trimul_out_hx_r<8>);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_trimul_contract_hx_big), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * CB_PLANE);
 #undef HX_ATTR
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_pair_transition_hx<8>), hipFuncAttributeMaxDynamicSharedMemorySize, HX_LDS_BYTES);

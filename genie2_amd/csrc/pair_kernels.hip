@@ -452,7 +452,7 @@ void launch_pair_static(genie_ctx* h, hipStream_t st) {
 void launch_pair_init(genie_ctx* h, hipStream_t st, const float* trans, const float* rots, const int8_t* codes) {
     ProfScope ps(h, st, KC_PAIR_INIT);
     const int N = h->N, ntile = (N + 63) / 64;
-    if (!h->has_motif && !getenv("GENIE_PAIR_STATIC_READ"))
+    if (!h->has_motif)
         hipLaunchKernelGGL(k_pair_init<true>, dim3(h->B * N * ntile), dim3(256), 0, st, trans, rots, codes, h->rmaskf, h->f_fstm,
                            h->pij, h->pstatic, h->templ_w, h->p, N, h->d.template_dist_min, h->d.template_dist_step,
                            h->d.template_dist_n_bin, h->f_ridx, h->f_cidx, h->relpos_t, h->d.relpos_k);

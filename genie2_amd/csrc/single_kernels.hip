@@ -851,7 +851,7 @@ __global__ __launch_bounds__(NW * 64) void k_struct_rows_hx(
     const float* g1, const float* be1, const unsigned char* __restrict__ W1, float i1, const float* b1,
     const unsigned char* __restrict__ W2, float i2, const float* b2, const unsigned char* __restrict__ W3, float i3, const float* b3,
     const float* g2, const float* be2, const float* bbw, const float* bbb, float* s_out, float* rots, float* trans, int M,
-    const float* trans_in, float* z_out, float inv_rescale, int nrb, unsigned long long* ts) {
+    const float* trans_in, float* z_out, float inv_rescale, int nrb) {
     constexpr int C = NW * 32, NT = NW * 64, KC = C / 16, NKC = C / 64;
     static_assert(C % 64 == 0 && NT >= 512 && NT <= 1024 && C + 4 <= SR_LD, "shape");
     extern __shared__ __attribute__((aligned(16))) float srm[];
@@ -863,8 +863,6 @@ __global__ __launch_bounds__(NW * 64) void k_struct_rows_hx(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = blockIdx.x * 32;
     const bool splitter = tid < 512;
-    int ts_n = 0;                                  // developer aid (GENIE_SR_TS=1): s_memtime at the phase boundaries of work-group 0
-    auto stamp = [&]() { if (ts && blockIdx.x == 0 && tid == 0) ts[ts_n++] = __builtin_amdgcn_s_memtime(); };
 
     if ((int)blockIdx.x >= nrb) {
         // The layer's three weight images (1.7 MB) were last used a whole denoiser step ago: they come from HBM, and a row
@@ -898,7 +896,6 @@ __global__ __launch_bounds__(NW * 64) void k_struct_rows_hx(
 #pragma unroll
         for (int u = 0; u < SR_PD; ++u) unit_issue(wb, wh[u], wl[u], u);
     };
-    stamp();
     ring_fill(W1);
 
     // s1 = sum of the output projection's split-K slices + its bias + the residual s (nsplit = 0: x is s1 itself); every load
@@ -1065,19 +1062,13 @@ __global__ __launch_bounds__(NW * 64) void k_struct_rows_hx(
         __syncthreads();
     };
 
-    stamp();
     layernorm(T0, g1, be1, nullptr);                      // T0 = s2
-    stamp();
     linear(T0, W1, W2, i1, b1, true, nullptr, T1);
-    stamp();
     linear(T1, W2, W3, i2, b2, true, nullptr, T1);
-    stamp();
     linear(T1, W3, nullptr, i3, b3, false, T0, T1);
-    stamp();
     for (int u = tid; u < 6 * C / 4; u += NT)             // BackboneUpdate weights -> T0 (visible after LayerNorm's barrier)
         reinterpret_cast<float4*>(T0)[u] = reinterpret_cast<const float4*>(bbw)[u];
     layernorm(T1, g2, be2, s_out);                        // T1 = s
-    stamp();
 
     // BackboneUpdate + frame composition (k_bb_update's arithmetic), 16 lanes per row; the update weights (6 x C) sit in T0,
     // whose last reader was the third Linear
@@ -1126,7 +1117,6 @@ __global__ __launch_bounds__(NW * 64) void k_struct_rows_hx(
             }
         }
     }
-    stamp();
 }
 
 // ---------------------------------------------------------------------------
@@ -1253,10 +1243,9 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
                                                     const float* __restrict__ rots, const float* __restrict__ trans,
                                                     const float* __restrict__ rmask, const float* __restrict__ head_w,
                                                     float* __restrict__ cat, int B, int N, int layer, int rev,
-                                                    const unsigned* __restrict__ pmax, unsigned long long* ts, int b0,
+                                                    const unsigned* __restrict__ pmax, int b0,
                                                     const float* __restrict__ vf, const float* __restrict__ vmax) {
-    constexpr int NT = MF ? 128 * Q : 512;       // 512 threads (Q = 4), or 1024 with Q = 8: two waves per query in o_pair, and every key / value
-                                                 // fetched through the L1 then serves eight queries
+    constexpr int NT = MF ? 128 * Q : 512;       // 512 threads (Q = 4): two waves per query in o_pair
     constexpr int CP = 128, HC = H * C, NQP = H * PQ * 3, NPT = H * PV * 3, NCAT = HC + H * PV * 4 + H * CP, HH = H / (NT / 256);
     static_assert(H % (NT / 256) == 0 && C % 4 == 0 && HC + NPT <= 512, "shape");
     static_assert(!MF || H <= 16, "matrix-pipe o_pair: 2 Q waves = Q queries x 2 channel halves");
@@ -1277,10 +1266,6 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
     const int bid = rev ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
     const int b = b0 + bid / groups, i0 = (bid % groups) * Q;       // the grid covers batch entries b0 .. (B stays the tensor's batch count)
     const int nq = min(Q, N - i0);
-    int ts_n = 0;                                  // developer aid (GENIE_SR_TS=1): s_memtime at the phase boundaries of work-group 0
-    auto stamp = [&]() { if (ts && blockIdx.x == 0 && tid == 0) ts[ts_n++] = __builtin_amdgcn_s_memtime(); };
-    stamp();
-    if (ts && tid == 0 && (blockIdx.x & 63) == 0) ts[16 + (blockIdx.x >> 6)] = __builtin_amdgcn_s_memtime();     // start of work-groups 0, 64, ...
     for (int u = tid; u < Q * HC; u += NT) { const int q = u / HC; sq[u] = proj[(size_t)(b * N + min(i0 + q, N - 1)) * ldp + (u - q * HC)]; }
     for (int u = tid; u < Q * NQP; u += NT) { const int q = u / NQP; sqp[u] = qp[(size_t)(b * N + min(i0 + q, N - 1)) * NQP + (u - q * NQP)]; }
     if (tid < H) {
@@ -1289,7 +1274,6 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
         shw[tid] = sp * sqrtf(1.0f / (3.0f * ((float)PQ * 9.0f / 2.0f)));
     }
     __syncthreads();
-    stamp();
     const float s_qk = sqrtf(1.0f / (3.0f * (float)C)), s_b = sqrtf(1.0f / 3.0f);
     {
         const int hg = tid >> 8;                 // heads hg*HH .. hg*HH + HH - 1
@@ -1339,7 +1323,6 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
         }
     }
     __syncthreads();
-    stamp();
     // softmax over j: 16 lanes per row (four rows per wave and round), float4 passes over LDS, reductions as four DPP steps
     // within the 16-lane row -- the one-wave-per-row form spent 12 dependent ds_bpermute round trips per row
     {
@@ -1374,15 +1357,12 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
         }
     }
     __syncthreads();
-    stamp();
     // o and o_pt.  MF: on the matrix pipe -- per head one 16 x 16 x 32 tile per column block (16 channels of v, 24 point coordinates in two
     // blocks) and 32 keys: A = the attention rows of the Q queries (rows Q.. are zero), split under the scale 2^14; B = the f32
     // fragments k_ipa_prep left, split here under one scale per structure for v and one for the points (largest magnitude to
     // [2^13, 2^14)).  Wave w takes heads 3 (w >> 1) .. + 2 and the key half w & 1; the two partial sums per output meet in LDS
     // (osum) after o_pair.  As a per-thread dot product (below, MF = 0) this phase was the kernel's second largest: 2.5 k vector
     // instructions per thread.
-    // Wave layout: Q = 4 (8 waves) -- heads 3 (w >> 1) .. + 2 and the key half w & 1, the two partial sums per output meet in LDS (osum)
-    // after o_pair; Q = 8 (16 waves) -- wave w < 12 takes head w over all keys and writes its results itself.
     constexpr int JP = MF ? (NT / 64 >= H ? 1 : 2) : 1;      // key parts
     constexpr int PARTS = JP;
     float* osum = opt + Q * NPT;                // [JP][Q][HC + NPT]   (JP = 2 only)
@@ -1515,7 +1495,6 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
             }
         }
     }
-    stamp();
     if constexpr (MF) {
         const int q = wave >> 1, hc = wave & 1, m = lane & 15, g = lane >> 4;
         if (q < nq) {
@@ -1624,7 +1603,6 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
         __syncthreads();
     }
     }
-    stamp();
     if constexpr (PARTS == 2) {                 // (after the barrier at the end of the o_pair branch)
         for (int u = tid; u < nq * (HC + NPT); u += NT) {
             const int q = u / (HC + NPT), col = u - q * (HC + NPT);
@@ -1791,19 +1769,14 @@ static bool ipa_is_base(const genie_dims_t& d) {
 static size_t ipa_attn_t1_lds(const genie_dims_t& d, int N) {      // k_ipa_attn_t<12, 16, 4, 8> (single query; long structures)
     return ((size_t)d.n_head_ipa * ((N + 7) & ~7) + 4 * d.n_head_ipa * d.c_p + d.n_head_ipa * d.n_v_point * 3) * sizeof(float);
 }
-#define IPA_Q8 8             // queries per work-group of the 1024-thread matrix-pipe form
-static size_t ipa_attn_q_lds(const genie_dims_t& d, int N, bool mf = false, int Q = IPA_Q);
-static bool ipa_use_q8(const genie_dims_t& d, int N) {
-    // measured slower (80.5 vs 76.0 us per launch): opt-in; read per call so that a test can compare both forms
-    return getenv("GENIE_IPA_Q8") != nullptr && ipa_attn_q_lds(d, N, true, IPA_Q8) <= 160 * 1024;
-}
+static size_t ipa_attn_q_lds(const genie_dims_t& d, int N, bool mf = false);
 static bool ipa_use_q(const genie_dims_t& d, int N) { return ipa_attn_q_lds(d, N) <= 160 * 1024; }
 static size_t ipa_attn_t_lds(const genie_dims_t& d, int N) { return ipa_use_q(d, N) ? ipa_attn_q_lds(d, N) : ipa_attn_t1_lds(d, N); }
-static size_t ipa_attn_q_lds(const genie_dims_t& d, int N, bool mf, int Q) {   // k_ipa_attn_q<12, 16, 4, 8, Q, mf>: no reduction buffer with mf
-    const size_t H = d.n_head_ipa;
-    return ((size_t)Q * H * (((N + 7) & ~7) + 4) + Q * H * d.c_hidden_ipa + Q * H * d.n_qk_point * 3 + 16 +
+static size_t ipa_attn_q_lds(const genie_dims_t& d, int N, bool mf) {   // k_ipa_attn_q<12, 16, 4, 8, IPA_Q, mf>: no reduction buffer with mf
+    const size_t H = d.n_head_ipa, Q = IPA_Q;
+    return (Q * H * (((N + 7) & ~7) + 4) + Q * H * d.c_hidden_ipa + Q * H * d.n_qk_point * 3 + 16 +
             Q * H * d.n_v_point * 3 + (mf ? 0 : 4 * H * d.c_p) +
-            (mf && Q == IPA_Q ? 2 * Q * H * (d.c_hidden_ipa + 3 * d.n_v_point) : 0)) * sizeof(float);       // mf, Q = 4: the two key halves' partial o / o_pt
+            (mf ? 2 * Q * H * (d.c_hidden_ipa + 3 * d.n_v_point) : 0)) * sizeof(float);       // mf: the two key halves' partial o / o_pt
 }
 size_t ipa_attn_lds(const genie_dims_t& d, int N) {
     if (ipa_is_base(d)) return ipa_attn_t_lds(d, N);
@@ -1831,29 +1804,14 @@ void launch_ipa_attn(genie_ctx* h, hipStream_t st, int layer, const float* head_
     if (ipa_is_base(d)) {
         const dim3 grid(nb * ((h->N + IPA_Q - 1) / IPA_Q));
         const int rev = (int)((layer ^ h->hx_launches ^ 1) & 1);
-        static unsigned long long* ts = nullptr;
-        if (!ts && getenv("GENIE_SR_TS")) (void)hipMalloc((void**)&ts, 64 * sizeof(unsigned long long));
-        if (h->hx && ipa_use_q8(d, h->N))
-            hipLaunchKernelGGL((k_ipa_attn_q<12, 16, 4, 8, IPA_Q8, 1>), dim3(nb * ((h->N + IPA_Q8 - 1) / IPA_Q8)), dim3(1024),
-                               ipa_attn_q_lds(d, h->N, true, IPA_Q8), st, h->proj, ldp, h->kT, h->v, h->qp, h->kpT, h->vp, h->ipa_bias, h->p,
-                               h->rots_w, h->trans_w, h->rmaskf, head_w, h->cat, h->B, h->N, layer, rev, h->pmax, ts, b0, h->vf, h->vmax);
-        else if (h->hx)
+        if (h->hx)
             hipLaunchKernelGGL((k_ipa_attn_q<12, 16, 4, 8, IPA_Q, 1>), grid, dim3(512), ipa_attn_q_lds(d, h->N, true), st, h->proj, ldp,
                                h->kT, h->v, h->qp, h->kpT, h->vp, h->ipa_bias, h->p, h->rots_w, h->trans_w, h->rmaskf, head_w, h->cat,
-                               h->B, h->N, layer, rev, h->pmax, ts, b0, h->vf, h->vmax);
+                               h->B, h->N, layer, rev, h->pmax, b0, h->vf, h->vmax);
         else
             hipLaunchKernelGGL((k_ipa_attn_q<12, 16, 4, 8, IPA_Q, 0>), grid, dim3(512), ipa_attn_q_lds(d, h->N), st, h->proj, ldp,
                                h->kT, h->v, h->qp, h->kpT, h->vp, h->ipa_bias, h->p, h->rots_w, h->trans_w, h->rmaskf, head_w, h->cat,
-                               h->B, h->N, layer, rev, h->pmax, ts, b0, nullptr, nullptr);
-        if (ts) {
-            unsigned long long v[24] = {0};
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(v, ts, sizeof(v), hipMemcpyDeviceToHost);
-            fprintf(stderr, "ipa_attn wg0 (cycles): q-load %llu logits %llu softmax %llu o/o_pt %llu o_pair %llu total %llu; starts of wg 64k:", v[1] - v[0],
-                    v[2] - v[1], v[3] - v[2], v[4] - v[3], v[5] - v[4], v[5] - v[0]);
-            for (int k = 0; k < 8; ++k) fprintf(stderr, " %lld", (long long)(v[16 + k] - v[0]));
-            fprintf(stderr, "\n");
-        }
+                               h->B, h->N, layer, rev, h->pmax, b0, nullptr, nullptr);
         return;
     }
     hipLaunchKernelGGL(k_ipa_attn, dim3(h->B * h->N), dim3(256), ipa_attn_lds(d, h->N), st, h->proj, ldp, h->kT, h->v, h->qp,
@@ -1894,20 +1852,11 @@ bool launch_struct_tail(genie_ctx* h, hipStream_t st, const StructLayerW& S, con
                            w0->img, cs, w0->inv_s, nullptr, nullptr, 0, nullptr, 0, h->spart + r0 * cs, cs, zs);
     }
     ProfScope ps(h, st, KC_STRUCT_ROWS);
-    static unsigned long long* ts = nullptr;
-    if (!ts && getenv("GENIE_SR_TS")) (void)hipMalloc((void**)&ts, 64 * sizeof(unsigned long long));
     const int nrb = (M + 31) / 32;                 // row work-groups; + 64 L2 prefetchers (8 per XCD) on CUs the rows leave idle
     hipLaunchKernelGGL((k_struct_rows_hx<12>), dim3(nrb + 64), dim3(768), struct_rows_lds(), st, h->spart + r0 * cs, SR_KSPLIT, zs, S.out_b, h->s + r0 * cs,
                        S.ln_ipa_g, S.ln_ipa_b, w1->img, w1->inv_s, S.t1_b, w2->img, w2->inv_s, S.t2_b, w3->img, w3->inv_s, S.t3_b,
                        S.ln_tr_g, S.ln_tr_b, S.bb_w, S.bb_b, h->s + r0 * cs, h->rots_w + r0 * 9, h->trans_w + r0 * 3, M, trans_in ? trans_in + r0 * 3 : nullptr,
-                       z_out ? z_out + r0 * 3 : nullptr, 1.0f / h->d.rescale, nrb, ts);
-    if (ts) {
-        unsigned long long v[8] = {0};
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(v, ts, sizeof(v), hipMemcpyDeviceToHost);
-        fprintf(stderr, "struct_rows wg0 (100 MHz ticks): load %llu ln %llu lin1 %llu lin2 %llu lin3 %llu ln %llu bb %llu total %llu\n", v[1] - v[0],
-                v[2] - v[1], v[3] - v[2], v[4] - v[3], v[5] - v[4], v[6] - v[5], v[7] - v[6], v[7] - v[0]);
-    }
+                       z_out ? z_out + r0 * 3 : nullptr, 1.0f / h->d.rescale, nrb);
     return true;
 }
 
@@ -1974,8 +1923,6 @@ void single_kernels_init(const genie_dims_t& d, int n_max) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ipa_attn_q_lds(d, n_max));
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ipa_attn_q<12, 16, 4, 8, IPA_Q, 1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ipa_attn_q_lds(d, n_max, true));
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ipa_attn_q<12, 16, 4, 8, IPA_Q8, 1>),       // (used up to the N that fits)
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(ipa_attn_q_lds(d, n_max, true, IPA_Q8), 160 * 1024));
         } else
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ipa_attn_t<12, 16, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)ipa_attn_t1_lds(d, n_max));

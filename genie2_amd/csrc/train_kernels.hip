@@ -29,15 +29,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // caller's flat state_dict blob often are not (a 6-float bias shifts everything behind it) and are fetched dword by dword.
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-#ifndef GM_BK
 #define GM_BK 32         // K per step: 32 -> 30 KiB of LDS with three pieces, four work-groups per CU (their phases interleave)
-#endif
-#define GM_LD (GM_BK + 8)   // row stride 80 B (144 B for 64): fragment reads and packed stores are conflict-free
+#define GM_LD (GM_BK + 8)   // row stride 80 B: fragment reads and packed stores are conflict-free
 #define GM_NV (GM_BK / 16)  // float4 per thread and operand tile
-#define GM_WPS (GM_BK == 32 ? 4 : 2)
-#ifndef GM_EXP
-#define GM_EXP 0      // developer knock-outs (tools/probe/gemm_variants.sh): 1 no MFMA, 2 no global loads, 4 no result store, 8 hi piece only
-#endif
+#define GM_WPS 4            // work-groups per CU
 
 // `full` (rows_left >= 64 and k_left >= GM_BK) is uniform over the work-group: full tiles -- nearly all of them -- load without a
 // per-lane test, so that a step's float4 go out back to back; edge tiles test every element.
@@ -107,7 +102,6 @@ __device__ __forceinline__ void gm_put(__bf16 (*S)[ROWS][GM_LD], int row, int k,
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
         h[j] = (__bf16)x[j];
-        if (GM_EXP & 8) { m[j] = h[j]; l[j] = h[j]; continue; }
         if (TERMS > 1) {
             const float r1 = x[j] - (float)h[j];
             m[j] = (__bf16)r1;
@@ -181,15 +175,14 @@ __global__ __launch_bounds__(256, GM_WPS) void k_gemm(const GemmP p, const int v
     GmTile cur = rq;                                        // the tile of the step in LDS
     f32x16 acc = zero16();
     float4 va[GM_NV], vb[GM_NV];
-    if (GM_EXP & 2) for (int i = 0; i < GM_NV; ++i) va[i] = vb[i] = make_float4(1.f, 2.f, 3.f, (float)tid);
     while (true) {
-        if (valid && !(GM_EXP & 2)) {
+        if (valid) {
             gm_load<AKC>(rq.A + (long long)rk * p.ak, p.am, p.ak, p.M - rq.m0, rq.kend - rk, vecA != 0, tid, va);
             gm_load<BKC>(rq.B + (long long)rk * p.bk, p.bn, p.bk, p.N - rq.n0, rq.kend - rk, vecB != 0, tid, vb);
         }
         if (have) {
 #pragma unroll
-            for (int c = 0; c < ((GM_EXP & 1) ? 0 : GM_BK / 16); ++c) {
+            for (int c = 0; c < GM_BK / 16; ++c) {
                 const int ko = c * 16 + 8 * (lane >> 5);
                 const bf16x8 ah = *reinterpret_cast<const bf16x8*>(&As[0][wm * 32 + (lane & 31)][ko]);
                 const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&Bs[0][wn * 32 + (lane & 31)][ko]);
@@ -210,7 +203,7 @@ __global__ __launch_bounds__(256, GM_WPS) void k_gemm(const GemmP p, const int v
             }
             if (last) {
                 const int col = cur.n0 + wn * 32 + (lane & 31);
-                if (col < p.N && !((GM_EXP & 4) && acc[0] != 12345.f)) {
+                if (col < p.N) {
                     const float bv = (p.bias && cur.sp == 0) ? p.bias[col] : 0.f;
                     const float al = p.colscale ? p.alpha * p.colscale[col] : p.alpha;
 #pragma unroll
@@ -535,13 +528,11 @@ static int gemm_kernel_choice(const GemmP& p) {
     const bool ua = p.ak == 1 || p.am == 1, ub = p.bk == 1 || p.bn == 1;
     const long long ks = ((p.K + p.nsplit - 1) / p.nsplit + GM_BK - 1) / GM_BK * GM_BK;
     const long long lim = 1LL << 24;              // a lane offset is at most 64 rows (or GM_BK k) of such a stride
-    static const bool off = getenv("GENIE_GEMM_GENERIC") != nullptr;
-    const bool fast = !off && ua && ub && p.M % 64 == 0 && p.N % 64 == 0 && p.K % GM_BK == 0 && ks % GM_BK == 0 && p.am < lim && p.ak < lim && p.bk < lim &&
+    const bool fast = ua && ub && p.M % 64 == 0 && p.N % 64 == 0 && p.K % GM_BK == 0 && ks % GM_BK == 0 && p.am < lim && p.ak < lim && p.bk < lim &&
                       p.bn < lim && (long long)p.batch * p.nsplit < 65536 && p.M / 64 < 65536;
     if (!fast) return 0;
-    static const bool nobig = getenv("GENIE_GEMM_NO_BIG") != nullptr;
     const long long big_tiles = (long long)(p.M / 128) * (p.N / 128) * p.batch * p.nsplit;
-    const bool use_big = !nobig && p.M % 128 == 0 && p.N % 128 == 0 && (big_tiles >= 256 || (big_tiles >= 192 && (p.M / 128) * (p.N / 128) >= 2));
+    const bool use_big = p.M % 128 == 0 && p.N % 128 == 0 && (big_tiles >= 256 || (big_tiles >= 192 && (p.M / 128) * (p.N / 128) >= 2));
     return use_big ? 2 : 1;
 }
 bool gemm_takes_mask(const GemmP& p) { return p.cblk == 0 && p.batch == 1 && p.mode == 0 && p.cn == 1 && p.cm == p.N && gemm_kernel_choice(p) == 2; }
@@ -570,8 +561,7 @@ void launch_gemm(hipStream_t st, const GemmP& p_in, int terms) {
             return;
         }
         if (fast) {
-            static const bool noxcd = getenv("GENIE_GEMM_NO_XCD") != nullptr;
-            p.xcd = (!noxcd && p.batch == 1 && p.nsplit >= 8 && p.nsplit % 8 == 0) ? 1 : 0;
+            p.xcd = (p.batch == 1 && p.nsplit >= 8 && p.nsplit % 8 == 0) ? 1 : 0;
 
             const bool akc = p.ak == 1, bkc = p.bk == 1;
             if (p.asum && (akc || p.batch != 1)) { launch_colsum(st, p.A, nullptr, p.K, p.M, p.asum, nullptr, p.ak); p.asum = nullptr; }
@@ -607,9 +597,7 @@ void launch_gemm(hipStream_t st, const GemmP& p_in, int terms) {
 }
 // split-K factor for a reduction of length K into `tiles` output tiles (x batch): enough work-groups to fill the chip, at least 128 of
 // K each.  Only for mode 2 (atomic accumulation).
-#ifndef GM_SPLIT_WGS
 #define GM_SPLIT_WGS 512      // work-groups of a multi-tile split-K GEMM: two per CU, so that one's operand staging runs under the other's MFMAs
-#endif
 int gemm_splits(long long M, long long N, long long K, long long batch) {
     // several 128 x 128 output tiles: one work-group of the 128-tile kernel per CU (its LDS admits one) -- the 64-tile kernel spends
     // more vector-ALU time splitting its operand tiles into bf16 pieces than the matrix pipe spends on them (a 64 x 64 tile has half
@@ -994,14 +982,12 @@ void launch_pair_sum_bwd(hipStream_t st, const float* dp, float* dpi, float* dpj
 // (modules/invariant_point_attention.py:100-260).  Row-major inputs straight from the projection GEMMs:
 //   q [M][H C], kv [M][H][2C] (k, then v), global-frame points qp [M][H][Pq][3], kp [M][H][Pq][3], vp [M][H][Pv][3],
 //   bias [B N N][H] = linear_b(p), p [B N N][cp].  One work-group per query (b, i).
-struct IpaDims { int B, N, H, C, Pq, Pv, cp; float c_qk, c_b; int skip; };     // skip: developer knock-out mask (GENIE_IPA_SKIP), 0 in use
+struct IpaDims { int B, N, H, C, Pq, Pv, cp; float c_qk, c_b; };
 __device__ __forceinline__ float softplus_dev(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
 // The IPA training kernels run one block per (b, i) query or key row -- B N blocks, two per CU at N = 256, batch 2 -- and are bound by
 // the latency of their loops: IPA_NT threads per block decide how many waves a CU has to hide it with.
-#ifndef IPA_NT
 #define IPA_NT 1024
-#endif
 template <int HT>      // head count at compile time (0: d.H) -- the per-head loops are unrolled over registers
 __global__ __launch_bounds__(IPA_NT) void k_ipa_fwd(IpaDims d, const float* __restrict__ q, const float* __restrict__ kv, const float* __restrict__ qp,
                                                  const float* __restrict__ kp, const float* __restrict__ vp, const float* __restrict__ bias,
@@ -1163,7 +1149,7 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_q(IpaDims d, const float* __
     __syncthreads();
     if (tid < 9) dR[(size_t)bi * 9 + tid] += red[tid];
     else if (tid < 12) dT[(size_t)bi * 3 + tid - 9] += red[tid];
-    if (!(d.skip & 1)) {   // d att[h][j] = <d o[h], v_j> + <d o_pt[h], v_pt_j> + <d o_pair[h], p[b,i,j,:]>.  The pair rows come through LDS in tiles
+    {   // d att[h][j] = <d o[h], v_j> + <d o_pt[h], v_pt_j> + <d o_pair[h], p[b,i,j,:]>.  The pair rows come through LDS in tiles
         // of 64 (coalesced; a lane reading its own 512-B row channel by channel touches 64 lines per instruction); thread (j, wave)
         // accumulates heads wave, wave + 4, ... so that one LDS read of p feeds every head of the thread
         float* pt = red + 16;               // [64][cp + 1]
@@ -1272,7 +1258,7 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_q(IpaDims d, const float* __
         if (pair_mfma) __syncthreads();
     }
     const float cpt = sqrtf(1.0f / (3.0f * ((float)Pq * 9.0f / 2.0f)));
-    if (!(d.skip & 2)) {   // d logits = att (d att - sum_j att d att); d head_weights, d bias of linear_b
+    {   // d logits = att (d att - sum_j att d att); d head_weights, d bias of linear_b
         const int wave = tid >> 6, lane = tid & 63;
         for (int h = wave; h < H; h += IPA_NT / 64) {
             float s = 0.f;
@@ -1316,19 +1302,19 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_q(IpaDims d, const float* __
         float* part = red + 16;                                        // [G][nout]
         const int o = tid % nout, g = tid / nout;
         if (G == 0) {           // more outputs than threads (not a released shape): every output walks all keys
-            for (int u = tid; u < ((d.skip & 4) ? 0 : nq); u += IPA_NT) {
+            for (int u = tid; u < nq; u += IPA_NT) {
                 const int h = u / C, c = u % C;
                 float sacc = 0.f;
                 for (int j = 0; j < N; ++j) sacc += dat[h * N + j] * kv[(((size_t)b * N + j) * H + h) * 2 * C + c];
                 dq[(size_t)bi * nq + u] = sacc * d.c_qk;
             }
-            for (int u = tid; u < ((d.skip & 8) ? 0 : np); u += IPA_NT) {
+            for (int u = tid; u < np; u += IPA_NT) {
                 const int h = u / (Pq * 3), t = u % (Pq * 3);
                 float sacc = 0.f;
                 for (int j = 0; j < N; ++j) sacc += dat[h * N + j] * (sqp[u] - kp[(((size_t)b * N + j) * H + h) * Pq * 3 + t]);
                 dqp[(size_t)bi * np + u] = -softplus_dev(head_w[h]) * cpt * sacc;
             }
-        } else if (g < G && !(o < nq ? (d.skip & 4) : (d.skip & 8))) {
+        } else if (g < G) {
             const int jb = (int)((long long)N * g / G), je = (int)((long long)N * (g + 1) / G);
             float sacc = 0.f;
             if (o < nq) {
@@ -1344,7 +1330,7 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_q(IpaDims d, const float* __
             part[g * nout + o] = sacc;
         }
         __syncthreads();
-        if (G > 0 && tid < nout && !(tid < nq ? (d.skip & 4) : (d.skip & 8))) {
+        if (G > 0 && tid < nout) {
             float sacc = 0.f;
             for (int gg = 0; gg < G; ++gg) sacc += part[gg * nout + tid];
             if (tid < nq) dq[(size_t)bi * nq + tid] = sacc * d.c_qk;
@@ -1356,7 +1342,6 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_q(IpaDims d, const float* __
         __syncthreads();
     }
     // pair gradient rows (b, i, j, :) += sum_h att do_pair + c_b dlogit W_b
-    if (d.skip & 16) return;
     if (IPA_NT % cp == 0 && H <= 16) {         // a thread keeps its channel: its column of d o_pair and W_b stays in registers
         const int c = tid % cp;
         float so[16], sw[16];
@@ -1424,12 +1409,6 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_k(IpaDims d, const float* __
         dvp[(size_t)bj * H * Pv * 3 + u] = s;
     }
 }
-// developer knock-out of sections of the IPA kernels (wrong gradients by design): only in -DGENIE_DEV builds (GENIE_EXTRA_FLAGS)
-#ifdef GENIE_DEV
-static int ipa_skip() { static const int v = getenv("GENIE_IPA_SKIP") ? atoi(getenv("GENIE_IPA_SKIP")) : 0; return v; }
-#else
-static int ipa_skip() { return 0; }
-#endif
 size_t ipa_train_lds(int N, int H, int C, int Pq, int Pv, int cp) {
     return (size_t)(2 * H * N + 2 * H * C + H * Pv * 3 + H * cp + H * Pq * 3 + 16) * sizeof(float);
 }
@@ -1440,7 +1419,7 @@ static void launch_ipa_fwd_t(hipStream_t st, const IpaArgs& a, const IpaDims& d,
                        a.head_w, a.att, a.cat);
 }
 void launch_ipa_fwd(hipStream_t st, const IpaArgs& a) {
-    IpaDims d{a.B, a.N, a.H, a.C, a.Pq, a.Pv, a.cp, sqrtf(1.0f / (3.0f * a.C)), sqrtf(1.0f / 3.0f), ipa_skip()};
+    IpaDims d{a.B, a.N, a.H, a.C, a.Pq, a.Pv, a.cp, sqrtf(1.0f / (3.0f * a.C)), sqrtf(1.0f / 3.0f)};
     // the forward kernel lays out att [H N], q, q points, output points, then the o_pair exchange buffer [IPA_NT / cp / 2][H][cp]
     const size_t lds = (size_t)(a.H * a.N + a.H * a.C + a.H * a.Pq * 3 + a.H * a.Pv * 3 + (IPA_NT % a.cp == 0 ? (IPA_NT / a.cp / 2) * a.H * a.cp : 0)) * sizeof(float);
     if (a.H == 12) launch_ipa_fwd_t<12>(st, a, d, lds);     // the released models' head count
@@ -1456,7 +1435,7 @@ static void launch_ipa_bwd_t(hipStream_t st, const IpaArgs& a, const IpaDims& d,
                        a.dkp, a.dvp);
 }
 void launch_ipa_bwd(hipStream_t st, const IpaArgs& a) {
-    IpaDims d{a.B, a.N, a.H, a.C, a.Pq, a.Pv, a.cp, sqrtf(1.0f / (3.0f * a.C)), sqrtf(1.0f / 3.0f), ipa_skip()};
+    IpaDims d{a.B, a.N, a.H, a.C, a.Pq, a.Pv, a.cp, sqrtf(1.0f / (3.0f * a.C)), sqrtf(1.0f / 3.0f)};
     const size_t lds = ipa_train_lds(a.N, a.H, a.C, a.Pq, a.Pv, a.cp);
     const size_t lds_q = lds + (size_t)64 * (a.cp + 1) * sizeof(float);            // + the staged tile of pair rows
     if (a.H == 12) launch_ipa_bwd_t<12>(st, a, d, lds, lds_q);

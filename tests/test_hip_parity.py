@@ -171,16 +171,24 @@ def _case(name, g):
         O.add_motif(f, 1, torch.randn(4, 3, generator=g) * 4, [0, 1, 16, 17])
     elif name == 'n2_tiny':
         f = O.empty_features([3, 2])
+    elif name == 'n40_b2_nine_layers':
+        f = O.empty_features([40, 33])
     else:
         raise KeyError(name)
     return f
 
 
-@pytest.mark.parametrize('name', ['n70_b3_ragged', 'n130_b1', 'n20_multichain_motif', 'n2_tiny'])
-@pytest.mark.parametrize('rescale,math', [(1.0, 'hx'), (2.0, 'hx'), (1.0, 'f32')])
+# every case in both arithmetics; plus hx with nine structure layers: 9 x 12 = 108 pair-bias rows > 96, so the pair bias and the
+# max |p| the hx attention scales p by come from the f32 kernel k_ipa_bias instead of k_ipa_bias_hx
+_SMALL_PARAMS = [(n, r, m) for r, m in [(1.0, 'hx'), (2.0, 'hx'), (1.0, 'f32')]
+                 for n in ['n70_b3_ragged', 'n130_b1', 'n20_multichain_motif', 'n2_tiny']] + [('n40_b2_nine_layers', 1.0, 'hx')]
+_CASE_DIMS = {'n40_b2_nine_layers': dict(n_structure_layer=9)}
+
+
+@pytest.mark.parametrize('name,rescale,math', _SMALL_PARAMS, ids=[f'{r}-{m}-{n}' for n, r, m in _SMALL_PARAMS])
 def test_denoiser_matches_oracle_small_dims(name, rescale, math):
     from genie2_amd.engine import GenieEngine
-    dims = O.small_dims(rescale=rescale)
+    dims = O.small_dims(rescale=rescale, **_CASE_DIMS.get(name, {}))
     sd = O.synthetic_state_dict(dims, seed=3)
     g = torch.Generator().manual_seed(9)
     f = _case(name, g)
@@ -378,8 +386,7 @@ def test_sampler_api_end_to_end(tmp_path, base_weights):
 def test_fused_structure_tail_matches_separate_launches(base_engine, monkeypatch):
     """k_struct_rows_hx (split-K output projection summed on load, LayerNorm, transition, LayerNorm, BackboneUpdate in
     one launch) against the seven separate launches it replaces (GENIE_NO_STRUCT_FUSE): same arithmetic up to summation
-    order.  Ragged batch whose row count is not a multiple of the 32-row tile.  The other alternative forms the library keeps
-    behind switches are run on the same inputs."""
+    order.  Ragged batch whose row count is not a multiple of the 32-row tile."""
     f = O.empty_features([45, 23, 38])
     B, N = f['residue_mask'].shape
     g = torch.Generator().manual_seed(11)
@@ -393,21 +400,11 @@ def test_fused_structure_tail_matches_separate_launches(base_engine, monkeypatch
     monkeypatch.setenv('GENIE_NO_STRUCT_FUSE', '1')
     zs = base_engine.denoise(x, r, ts, None, taps=('s_final',))
     monkeypatch.delenv('GENIE_NO_STRUCT_FUSE', raising=False)
-    monkeypatch.setenv('GENIE_IPA_Q8', '1')          # eight queries per 1024-thread attention work-group (opt-in form)
-    z8 = base_engine.denoise(x, r, ts, None, taps=('s_final',))
-    monkeypatch.delenv('GENIE_IPA_Q8', raising=False)
-    monkeypatch.setenv('GENIE_OUT_STREAMED', '1')    # TriMul output kernel with streamed weights, pair bias through the f32 kernel
-    monkeypatch.setenv('GENIE_IPA_BIAS_F32', '1')
-    zo = base_engine.denoise(x, r, ts, None, taps=('s_final',))
-    monkeypatch.delenv('GENIE_OUT_STREAMED', raising=False)
-    monkeypatch.delenv('GENIE_IPA_BIAS_F32', raising=False)
     m = f['residue_mask'].bool()           # padded rows attend through an all -1e5 bias: not comparable beyond summation order
     for k in ('z', 's_final'):
         a, b = zf[k].cpu()[m], zs[k].cpu()[m]
         assert torch.isfinite(a).all()
         assert mdiff(a, b) <= 4e-6 * max(1.0, float(b.abs().max())), k
-        assert mdiff(z8[k].cpu()[m], a) <= 4e-6 * max(1.0, float(b.abs().max())), k
-        assert mdiff(zo[k].cpu()[m], a) <= 2e-5 * max(1.0, float(b.abs().max())), k
 
 
 def test_training_step_ends_match_reference_golden(base_engine):
@@ -585,32 +582,3 @@ def test_two_stream_structure_net_is_bit_identical(base_engine, monkeypatch):
         assert torch.isfinite(res[0][k]).all(), k
         assert torch.equal(res[0][k], res[1][k]), k
 
-
-@pytest.mark.gpu
-def test_eight_query_attention_form_matches_the_default(base_engine, monkeypatch):
-    """GENIE_IPA_Q8 selects the attention kernel's 1024-thread form (eight queries per work-group, one head per wave in the a v / a v_pts
-    phase, no partial sums through LDS): same arithmetic in a different summation split, so the step's outputs must agree with the
-    four-query default to f32 rounding -- on a ragged batch whose last query group is partial for both forms."""
-    f = O.empty_features([250, 203, 117])
-    g = torch.Generator().manual_seed(21)
-    B, N = f['residue_mask'].shape
-    x = torch.randn(B, N, 3, generator=g) * 6
-    base_engine.set_math('hx')
-    base_engine.bind_features(f)
-    r = base_engine.frenet(x)
-    ts = torch.randint(1, 1001, (B,), generator=g).int()
-    taps = ('states', 'ipa_cat0', 'trans_out')
-    monkeypatch.delenv('GENIE_IPA_Q8', raising=False)
-    ref = base_engine.denoise(x, r, ts, None, taps=taps)
-    monkeypatch.setenv('GENIE_IPA_Q8', '1')
-    try:
-        out = base_engine.denoise(x, r, ts, None, taps=taps)
-    finally:
-        monkeypatch.delenv('GENIE_IPA_Q8', raising=False)
-    m = f['residue_mask'].float().to(ref['z'].device)
-    for k in ref:
-        assert torch.isfinite(out[k]).all(), k
-        w = m.reshape((1,) * (ref[k].dim() - 3) + (B, N, 1))                 # padded residues carry no meaning
-        scale = max(1.0, float((ref[k] * w).abs().max()))
-        d = float(((out[k] - ref[k]) * w).abs().max())
-        assert d <= 2e-5 * scale, (k, d, scale)
