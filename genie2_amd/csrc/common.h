@@ -232,7 +232,7 @@ struct genie_ctx {
     float *pij_w;                 // packed [256][384]: linear_s_p_i | linear_s_p_j
     float *relpos_t;              // [67][128] transposed raw
     float *templ_w;               // packed [128][48]
-    float *motif_w;               // packed [128][40]
+    float *motif_w;               // packed [128][48]
     float *ipa_bias_w, *ipa_bias_b;   // packed [ceil32(L*H)][128], [L*H]
     PairLayerW* pair;             // host arrays of device pointers
     StructLayerW* st;

@@ -297,17 +297,17 @@ int genie_load_weights(genie_handle_t h, const float* blob, size_t n_floats) {
         for (int o = 0; o < (int)cp; ++o) for (int k = 0; k < nr; ++k) t[(size_t)k * cp + o] = w[(size_t)o * nr + k];
         slot(&h->relpos_t, img.raw(t.data(), t.size()));
     }
-    {   // template: K padded to 48, motif: K padded to 40 (LDS tile widths of k_pair_init / k_pair_static)
+    {   // template (n_bin + 6 columns) and motif (n_bin + 2): K padded to 48, the LDS tile width of k_pair_init / k_pair_static
         const int kt = d.template_dist_n_bin + 6, km = d.template_dist_n_bin + 2;
         const float* wt = c.take(cp * kt);
         const float* wm = c.take(cp * km);
-        std::vector<float> t((size_t)cp * 48, 0.f), m((size_t)cp * 40, 0.f);
+        std::vector<float> t((size_t)cp * 48, 0.f), m((size_t)cp * 48, 0.f);
         for (int o = 0; o < (int)cp; ++o) {
             for (int k = 0; k < kt; ++k) t[(size_t)o * 48 + k] = wt[(size_t)o * kt + k];
-            for (int k = 0; k < km; ++k) m[(size_t)o * 40 + k] = wm[(size_t)o * km + k];
+            for (int k = 0; k < km; ++k) m[(size_t)o * 48 + k] = wm[(size_t)o * km + k];
         }
         slot(&h->templ_w, img.pack(t.data(), (int)cp, 48));
-        slot(&h->motif_w, img.pack(m.data(), (int)cp, 40));
+        slot(&h->motif_w, img.pack(m.data(), (int)cp, 48));
     }
     struct TmSave { std::vector<float> w, gw, zw; float sp, sg, sgo, szo; };
     struct PtSave { std::vector<float> w1v, w2; float s1, s2; };

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void k_pair_init(const float* __restrict__ tra
 // Step-invariant pair terms (pair_feature_net.py:134,149-158,166-221):
 //   static = W_relpos[:, d_ij] + same_chain * W_relpos[:, 66]
 //          + W_motif [bins(atom_positions) * fsm_i fsm_j * fstm_ij | fstm | fstm]
-#define LDM 44   // 40 features + 4 pad
+#define LDM 52   // 48 features + 4 pad: n_bin + 2 <= 42 columns of linear_motif_template, padded to six k-blocks of 8
 template <bool MOTIF>
 __global__ __launch_bounds__(256) void k_pair_static(const float* __restrict__ pos, const int32_t* __restrict__ ridx,
                                                      const int32_t* __restrict__ cidx, const uint8_t* __restrict__ fsm,
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256) void k_pair_static(const float* __restrict__ p
                 const float dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
                 const float d = sqrtf(1e-10f + ((dx * dx + dy * dy) + dz * dz));
                 soft_bins(frow, d, dmin, dstep, nbin, pm, part);
-                if (part == 0) { frow[nbin] = f; frow[nbin + 1] = f; for (int k = nbin + 2; k < 40; ++k) frow[k] = 0.f; }
+                if (part == 0) { frow[nbin] = f; frow[nbin + 1] = f; for (int k = nbin + 2; k < 48; ++k) frow[k] = 0.f; }
             }
             if (part == 0) {
                 const bool sc = cidx[b * N + i] == cidx[b * N + j];
@@ -393,15 +393,15 @@ __global__ __launch_bounds__(256) void k_pair_static(const float* __restrict__ p
                 same[jl] = sc ? 1.f : 0.f;
             }
         } else if (MOTIF) {
-            for (int k = part; k < 40; k += 4) frow[k] = 0.f;
+            for (int k = part; k < 48; k += 4) frow[k] = 0.f;
         }
     }
     __syncthreads();
     f32x16 a0 = zero16(), a1 = zero16();
     if (MOTIF) {
 #pragma unroll
-        for (int kb = 0; kb < 5; ++kb) {
-            const float4 w = wfrag(wm, 5, wave, kb, lane);
+        for (int kb = 0; kb < 6; ++kb) {
+            const float4 w = wfrag(wm, 6, wave, kb, lane);
             a0 = mfma_8k(lfrag(ft, LDM, 0, kb, lane), w, a0);
             a1 = mfma_8k(lfrag(ft, LDM, 32, kb, lane), w, a1);
         }

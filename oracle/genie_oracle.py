@@ -1,7 +1,7 @@
 """
 ORACLE -- TEST INFRASTRUCTURE ONLY.
 
-CPU (PyTorch fp32/fp64) restatement of the Genie 2 denoising hot path of
+CPU (PyTorch; float32, or float64 when given float64 weights and coordinates) restatement of the Genie 2 denoising hot path of
 marvinli00/genie2.  It is the checker for the HIP kernels in
 `genie2_amd/csrc` and the `cpu_baseline` ("port") leg of `bench.py`.
 Nothing under `genie2_amd/` imports this file; the product path never falls
@@ -307,8 +307,9 @@ def apply_sign_codes(q, codes):
 # encodings (genie/utils/encoding.py:5-25)
 # --------------------------------------------------------------------------
 
-def sinusoidal_encoding(v, N, D):
-    k = torch.arange(1, D + 1)
+def sinusoidal_encoding(v, N, D, dtype=torch.float32):
+    k = torch.arange(1, D + 1, dtype=dtype)
+    v = v.to(dtype)
     sin_div = N ** (2 * k / D)
     cos_div = N ** (2 * (k - 1) / D)
     sin_enc = torch.sin(v.unsqueeze(-1) * math.pi / sin_div)
@@ -333,10 +334,11 @@ def _ln(sd, key, x):
 
 def single_feature_net(sd, dims, timesteps, features, n_res):
     """single_feature_net.py:58-142."""
-    pos = sinusoidal_encoding(features['residue_index'], dims['max_n_res'], dims['c_pos_emb'])
-    chn = sinusoidal_encoding(features['chain_index'], dims['max_n_chain'], dims['c_chain_emb'])
+    dt = sd['single_feature_net.linear.weight'].dtype
+    pos = sinusoidal_encoding(features['residue_index'], dims['max_n_res'], dims['c_pos_emb'], dt)
+    chn = sinusoidal_encoding(features['chain_index'], dims['max_n_chain'], dims['c_chain_emb'], dt)
     s = timesteps.unsqueeze(-1).repeat(1, n_res)
-    tem = sinusoidal_encoding(s, dims['n_timestep'], dims['c_timestep_emb'])
+    tem = sinusoidal_encoding(s, dims['n_timestep'], dims['c_timestep_emb'], dt)
     fsm = features['fixed_sequence_mask']
     aat = features['aatype'] * fsm.unsqueeze(-1)
     x = torch.cat([pos, chn, tem, aat, fsm.unsqueeze(-1), fsm.unsqueeze(-1),
@@ -349,7 +351,7 @@ def soft_distance_bins(dims, coords, mask):
     distance has eps inside the sqrt (geo_utils.py:19)."""
     diff = coords.unsqueeze(2) - coords.unsqueeze(1)
     d = (1e-10 + torch.sum(diff ** 2, dim=-1)) ** 0.5
-    v = dims['template_dist_min'] + torch.arange(0, dims['template_dist_n_bin']) * dims['template_dist_step']
+    v = dims['template_dist_min'] + torch.arange(0, dims['template_dist_n_bin'], dtype=coords.dtype) * dims['template_dist_step']
     oh = F.softmax(-4.0 * torch.abs(d.unsqueeze(-1) - v), dim=-1)
     pm = mask.unsqueeze(1) * mask.unsqueeze(2)
     return oh * pm.unsqueeze(-1)
@@ -375,9 +377,9 @@ def relpos(sd, dims, features):
     same = ci[:, :, None] == ci[:, None, :]
     d_same = torch.clip(ri[:, :, None] - ri[:, None, :] + k, 0, 2 * k)
     d = d_same * same + (2 * k + 1) * (~same)
-    oh = F.one_hot(d.long(), num_classes=2 * k + 2).float()
-    return F.linear(torch.cat([oh, same.unsqueeze(-1).float()], dim=-1),
-                    sd['pair_feature_net.linear_relpos.weight'])
+    w = sd['pair_feature_net.linear_relpos.weight']
+    oh = F.one_hot(d.long(), num_classes=2 * k + 2).to(w.dtype)
+    return F.linear(torch.cat([oh, same.unsqueeze(-1).to(w.dtype)], dim=-1), w)
 
 
 def pair_feature_net(sd, dims, s, rots, trans, features, quat_mode='eigh', sign_codes=None, taps=None):
@@ -388,7 +390,7 @@ def pair_feature_net(sd, dims, s, rots, trans, features, quat_mode='eigh', sign_
     p_j = F.linear(s, sd['pair_feature_net.linear_s_p_j.weight'])
     p = p_i[:, :, None, :] + p_j[:, None, :, :]
     p = p + relpos(sd, dims, features)
-    fsm2 = features['fixed_structure_mask'].unsqueeze(-1).float()
+    fsm2 = features['fixed_structure_mask'].unsqueeze(-1).to(s.dtype)
     qm, q_raw = pair_orientations(rots, rm, quat_mode, sign_codes)
     if taps is not None:
         taps['quat'] = q_raw
@@ -426,7 +428,7 @@ def pair_transform_net(sd, dims, p, features, taps=None, dropout_masks=None):
     """pair_transform_net.py:91-119,224-232.  Dropouts are identity in eval; `dropout_masks` (train mode) maps
     ('tri', layer, 0 | 1) to the row-shared keep-mask [B,1,N,C] (already scaled by 1 / (1 - rate), modules/dropout.py:23-76)."""
     rm = features['residue_mask']
-    pm = (rm.unsqueeze(1) * rm.unsqueeze(2)).float()
+    pm = (rm.unsqueeze(1) * rm.unsqueeze(2)).to(p.dtype)
     dm = dropout_masks or {}
     for l in range(dims['n_pair_transform_layer']):
         pfx = f'pair_transform_net.net.{l}.'
@@ -503,7 +505,7 @@ def structure_net(sd, dims, s, p, rots, trans, features, taps=None, dropout_mask
     """structure_net.py:76-116,189-243 and modules/structure_transition.py:34-70.  `dropout_masks` (train mode):
     ('ipa', i) on s + ipa(s) (structure_net.py:109) and ('transition', i) before the transition's LayerNorm
     (structure_transition.py:66), i = running layer index, each [B,N,c_s] scaled by 1 / (1 - rate)."""
-    mask = features['residue_mask'].float()
+    mask = features['residue_mask'].to(s.dtype)
     dm = dropout_masks or {}
     states = [s]                                         # structure_net.py:236-243: input + s after every layer
     li = 0
@@ -534,8 +536,10 @@ def structure_net(sd, dims, s, p, rots, trans, features, taps=None, dropout_mask
 
 def denoiser_forward(sd, dims, rots, trans, timesteps, features, quat_mode='eigh',
                      sign_codes=None, taps=None, dropout_masks=None):
-    """model/model.py:125-192.  Returns dict(z, s, p, s_final, rots, trans)."""
+    """model/model.py:125-192.  Returns dict(z, s, p, s_final, rots, trans).  The arithmetic follows the dtype of the weights:
+    float64 weights, frames and coordinates give a float64 result (float32 motif coordinates in `features` are cast up)."""
     f = prepare_features(features)
+    f['atom_positions'] = f['atom_positions'].to(trans.dtype)
     trans0 = trans
     trans = trans * dims['rescale']
     N = trans.shape[1]
@@ -621,13 +625,14 @@ def train_dropout_masks(dims, B, N, seed, tri_dropout=0.25, ipa_dropout=0.1, tra
 
 
 def prepare_features(features):
-    """Same dtypes the model sees after feat_utils.py:304-321."""
+    """Same dtypes the model sees after feat_utils.py:304-321; float64 motif coordinates stay float64."""
     out = dict(features)
     for k in ('residue_mask', 'residue_index', 'chain_index', 'aatype'):
         out[k] = features[k].int() if k != 'aatype' else features[k].int()
     for k in ('fixed_sequence_mask', 'fixed_structure_mask', 'interface_mask'):
         out[k] = features[k].bool()
-    out['atom_positions'] = features['atom_positions'].float()
+    ap = features['atom_positions']
+    out['atom_positions'] = ap if ap.dtype == torch.float64 else ap.float()
     return out
 
 
@@ -686,7 +691,8 @@ def add_motif(features, b, motif_positions, motif_index, aatype_idx=None):
 
 def p_sample_step(sched, step, scale, trans, z_pred, eps, features):
     """base.py:249-282 for one step value (same for the whole batch).
-    Returns (new_trans, new_rots).  eps=None on the last step (step == 1)."""
+    Returns (new_trans, new_rots).  eps=None on the last step (step == 1).  Follows the dtype of `trans`: the float32
+    schedule terms are cast up by promotion."""
     mask = features['residue_mask'].unsqueeze(-1)
     w_z = (1. - sched['alphas'][step]) / sched['sqrt_one_minus_alphas_cumprod'][step]
     mean = (1. / sched['sqrt_alphas'][step]) * (trans - w_z * z_pred)

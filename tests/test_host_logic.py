@@ -63,6 +63,23 @@ def test_create_fails_loudly_without_gpu_or_bad_dims():
     h = C.c_void_p()
     rc = lib.genie_create(C.byref(capi.GenieDims(**bad)), 0, C.byref(h))
     assert rc == -1 and b'c_p' in lib.genie_last_error(None)
+    # every refusal INTEGRATION.md lists is made before the device is touched, with its own message; the supported edge next to
+    # each passes that check (without a GPU it then fails on the device instead, with another code)
+    for over, word in ((dict(c_s=132), b'c_s'), (dict(c_s=520), b'c_s'), (dict(n_head_ipa=17), b'n_head_ipa'),
+                       (dict(template_dist_n_bin=41), b'template_dist_n_bin'), (dict(template_dist_n_bin=0), b'template_dist_n_bin'),
+                       (dict(c_hidden_mul=64), b'c_hidden_mul'), (dict(n_structure_layer=0), b'layer counts'),
+                       (dict(n_pair_transform_layer=-1), b'layer counts'), (dict(pair_transition_n=0), b'bad dims'),
+                       (dict(n_head_ipa=5, c_hidden_ipa=3, n_v_point=8), b'multiples of 4')):
+        h = C.c_void_p()
+        rc = lib.genie_create(C.byref(capi.GenieDims(**dict(pack.BASE_DIMS, **over))), 0, C.byref(h))
+        assert rc == -1 and not h.value and word in lib.genie_last_error(None), (over, lib.genie_last_error(None))
+    for over in (dict(c_s=136), dict(c_s=512), dict(n_head_ipa=16), dict(n_head_ipa=5), dict(template_dist_n_bin=40),
+                 dict(template_dist_n_bin=1), dict(n_pair_transform_layer=0), dict(pair_transition_n=1), dict(relpos_k=0)):
+        h = C.c_void_p()
+        rc = lib.genie_create(C.byref(capi.GenieDims(**dict(pack.BASE_DIMS, **over))), 0, C.byref(h))
+        assert rc != -1, (over, lib.genie_last_error(None))
+        if rc == 0:
+            lib.genie_destroy(h)
     if not torch.cuda.is_available():
         from genie2_amd.engine import GenieEngine
         with pytest.raises(capi.GenieError):

@@ -137,3 +137,80 @@ def test_training_gradients_match_reference_golden(base_weights):
         assert abs(float(gr.norm()) - float(g['grad_norm'][i])) <= 5e-3 * max(float(g['grad_norm'][i]), 1e-6), k
         n = min(8, gr.numel())
         assert (gr.reshape(-1)[:n] - t(g['grad_probe'][i][:n])).abs().max() <= 5e-3 * scale, k
+
+
+def _as64(x):
+    return x.double() if torch.is_tensor(x) and x.is_floating_point() else x
+
+
+def _oracle_pair(dims, sd, f, rots, trans, ts, codes=None):
+    """(float32 result, float64 result) of the same call: weights, frames and coordinates cast up for the second."""
+    out = []
+    for cast in (lambda x: x, _as64):
+        taps = {}
+        o = O.denoiser_forward({k: cast(v) for k, v in sd.items()}, dims, cast(rots), cast(trans), ts, f, 'closed', codes, taps)
+        out.append(dict(z=o['z'], p=o['p'], states=taps['states']))
+    return out
+
+
+@pytest.mark.parametrize('case', ['uncond_n16_b1_t1000', 'motif_n40_b2_t300'])
+def test_float32_oracle_bits_are_pinned(case, base_weights):
+    """The float32 oracle is the reference of every parity test, so making it follow its inputs' dtype must not move it by a
+    bit: z, p and all states equal what the float32-only oracle gave for the same call (tests/golden/oracle_f32_pinned.npz:
+    SHA-256 of the three whole arrays, and every seventh residue's rows of p and of the states to name a difference).  One
+    BLAS thread and the correctly rounded sqrt, as when the values were recorded: the summation order of a threaded GEMM is
+    not fixed."""
+    import hashlib
+    pin = load_golden('oracle_f32_pinned')
+    g = load_golden('call_' + case)
+    f = golden_features(g)
+    B, N = f['residue_mask'].shape
+    ts = torch.full((B,), int(g['timestep']), dtype=torch.int32)
+    n_threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        with O.correctly_rounded_sqrt():
+            taps = {}
+            o = O.denoiser_forward(base_weights, dict(O.BASE_DIMS), t(g['rots']), t(g['trans']), ts, f, 'closed',
+                                   t(g['quat_codes']), taps)
+    finally:
+        torch.set_num_threads(n_threads)
+    rows = t(pin[case + '.rows']).long()
+    got = dict(z=o['z'], p=o['p'], states=taps['states'])
+    assert all(v.dtype == torch.float32 for v in got.values())
+    assert torch.equal(got['z'], t(pin[case + '.z']))
+    assert torch.equal(got['p'][:, rows], t(pin[case + '.p_rows']))
+    assert torch.equal(got['states'][:, :, rows], t(pin[case + '.states_rows']))
+    for k, v in got.items():
+        assert hashlib.sha256(v.contiguous().numpy().tobytes()).digest() == pin[case + '.' + k + '_sha256'].tobytes(), k
+
+
+@pytest.mark.parametrize('N', [64, 200])
+def test_float32_oracle_against_its_float64_self(N):
+    """What the float32 reference itself costs: small_dims, a ragged batch, float32 against float64 arithmetic on the same
+    inputs, relative to max(1, |x|_inf).  Measured 7e-6 at worst (p at N = 200); 2e-5 leaves room for another BLAS build and
+    is a fifth of the 1e-4 bar the kernels are held to."""
+    dims = O.small_dims()
+    sd = O.synthetic_state_dict(dims, seed=3)
+    f = O.empty_features([N, N // 2 + 1])
+    g = torch.Generator().manual_seed(N)
+    trans = 3.0 * torch.randn(2, N, 3, generator=g)
+    ts = torch.randint(1, dims['n_timestep'] + 1, (2,), generator=g, dtype=torch.int32)
+    fr = O.prepare_features(f)
+    rots = O.compute_frenet_frames(trans, fr['chain_index'], fr['residue_mask'])
+    r32, r64 = _oracle_pair(dims, sd, f, rots, trans, ts)
+    m = fr['residue_mask'].unsqueeze(-1).double()          # z and the states mean nothing on padding
+    for k in ('z', 'p', 'states'):
+        assert r32[k].dtype == torch.float32 and r64[k].dtype == torch.float64, k
+        w = 1.0 if k == 'p' else m
+        err = float(((r32[k].double() - r64[k]) * w).abs().max()) / max(1.0, float((r64[k] * w).abs().max()))
+        print(f'N={N} {k}: fp32 oracle vs float64 oracle {err:.2e}')
+        assert err <= 2e-5, (k, err)
+    # the geometry and the reverse step follow their coordinates too
+    r64f = O.compute_frenet_frames(trans.double(), fr['chain_index'], fr['residue_mask'])
+    assert r64f.dtype == torch.float64 and (r64f - rots.double()).abs().max() < 2e-6
+    sched = O.setup_schedule(dims['n_timestep'])
+    eps = torch.randn(2, N, 3, generator=g)
+    n32, _ = O.p_sample_step(sched, 40, 0.6, trans, r32['z'], eps, fr)
+    n64, q64 = O.p_sample_step(sched, 40, 0.6, trans.double(), r32['z'].double(), eps.double(), fr)
+    assert n64.dtype == torch.float64 and q64.dtype == torch.float64 and (n64 - n32.double()).abs().max() < 1e-5
