@@ -29,6 +29,7 @@ class GenieDims(C.Structure):
         ('c_hidden_ipa', C.c_int32), ('n_head_ipa', C.c_int32), ('n_qk_point', C.c_int32), ('n_v_point', C.c_int32),
         ('rescale', C.c_float),
         ('n_timestep', C.c_int32), ('max_n_res', C.c_int32), ('max_n_chain', C.c_int32),
+        ('c_hidden_tri_att', C.c_int32), ('n_head_tri', C.c_int32),      # zero tail = no triangular attention
     ]
 
 
@@ -40,7 +41,7 @@ class GenieFeatures(C.Structure):
 
 class GenieTaps(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ('s', 'p', 's_final', 'rots_out', 'trans_out', 'p_init', 'p_layer0', 'states', 'p_trimul_out0',
-                                              'ipa_cat0')]
+                                              'ipa_cat0', 'p_tri_att0')]
 
 
 class GenieGemmDesc(C.Structure):

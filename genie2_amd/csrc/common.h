@@ -174,7 +174,8 @@ enum KernelClass {
     KC_SINGLE_INPUT = 0, KC_GEMM_ROWS, KC_LAYERNORM, KC_PAIR_STATIC, KC_PAIR_INIT,
     KC_TRIMUL_PROJ, KC_TRIMUL_CONTRACT, KC_TRIMUL_OUT, KC_PAIR_TRANSITION,
     KC_IPA_BIAS, KC_IPA_PREP, KC_IPA_ATTN, KC_BB_UPDATE, KC_STRUCT_ROWS, KC_P_SAMPLE, KC_MISC, KC_PAIR_FUSED_A, KC_PAIR_FUSED_B,
-    KC_TR_GEMM, KC_TR_EW, KC_TR_LN, KC_TR_TRANSPOSE, KC_TR_IPA, KC_TR_MISC, KC_COUNT      // training path (genie_train.hip)
+    KC_TR_GEMM, KC_TR_EW, KC_TR_LN, KC_TR_TRANSPOSE, KC_TR_IPA, KC_TR_MISC,      // training path (genie_train.hip)
+    KC_TRIATT_PROJ, KC_TRIATT_CORE, KC_TRIATT_TRANSPOSE, KC_COUNT               // triangular attention (pair_triatt_kernels.hip)
 };
 
 // "hx" images (hx.h): weights split in f16 halves, in stage order, + the scales that go with them
@@ -195,8 +196,17 @@ struct TriMulW {
     float *ln_in_g, *ln_in_b, *ln_out_g, *ln_out_b;
     HxTriW hx;
 };
+// one TriangleAttention module (pair_triatt_kernels.hip); all NULL / 0 without the option
+struct TriAttW {
+    float *ln_g, *ln_b;       // raw LayerNorm affine [128]
+    float *wb;                // raw linear.weight [H][128] (the triangle bias)
+    float *proj_w, *proj_b;   // packed [512][128]: q | k | v | g;  [512]: zeros, then linear_g.bias
+    float *out_w, *out_b;     // packed [128][H c], [128]
+    float sq, sk, sv;         // hx scales of the attention core's q, k, v operands (from their weights' bounds)
+};
 struct PairLayerW {
     TriMulW out, in;
+    TriAttW ta_start, ta_end;
     float *pt_ln_g, *pt_ln_b, *pt_w1, *pt_b1, *pt_w2, *pt_b2;   // w1 packed [512][128], w2 packed [128][512]
     HxTransW hx_pt;
     HxFusedW fa, fb;          // chain A: out-output -> in-projections;  chain B: in-output -> transition -> next block's out-projections
@@ -225,7 +235,7 @@ struct genie_ctx {
     float* wdev;                  // one device allocation holding everything below
     bool hx;                      // pair-stack GEMMs in split-f16 arithmetic (hx.h); GENIE_MATH=f32 selects the f32-MFMA kernels
     unsigned char* hxdev;         // device allocation of the hx weight images
-    HxGemmW hxg[64]; int n_hxg;   // hx images of the row-GEMM weights
+    HxGemmW hxg[128]; int n_hxg;   // hx images of the row-GEMM weights
     unsigned hx_launches;         // pair-stack launches so far: its parity picks the tile direction of the next one
     size_t wdev_floats;
     float *single_w;              // packed [384][856]
@@ -259,6 +269,7 @@ struct genie_ctx {
     float *xsingle, *s0, *s, *s1, *s2, *h1, *h2, *pij, *proj, *cat;
     float *kT, *v, *qp, *kpT, *vp;
     float *vf, *vmax;      // hx attention: V / v_pts rows as f32 MFMA B fragments, and each row's largest |v|, |v_pt| (single_kernels.hip k_ipa_prep)
+    float *ta_tb, *ta_xn, *ta_qkvg;   // triangular attention (n_head_tri > 0): bias [B,H,N,NPK], one slab's LayerNorm output and q|k|v|g
     float *rots_w, *trans_w;      // working frames
     int32_t* tsteps;              // [B] uniform timestep buffer for the loop
     float *loop_z;                // [B,N,3]
@@ -278,7 +289,7 @@ struct genie_ctx {
 void launch_single_input(genie_ctx* h, hipStream_t st, const int32_t* timesteps);
 void launch_gemm_rows(genie_ctx* h, hipStream_t st, const float* A, int lda, int M, int K,
                       const float* Wp, int Nout, const float* bias, const float* res, int ldr,
-                      const float* rowmask, int relu, float* out, int ldo);
+                      const float* rowmask, int relu, float* out, int ldo, int prof_class = KC_GEMM_ROWS);
 void launch_layernorm_rows(genie_ctx* h, hipStream_t st, const float* in, float* out, int M, int C,
                            const float* g, const float* b);
 void launch_pair_static(genie_ctx* h, hipStream_t st);
@@ -286,6 +297,8 @@ void launch_pair_init(genie_ctx* h, hipStream_t st, const float* trans, const fl
                       const int8_t* codes);
 void launch_trimul(genie_ctx* h, hipStream_t st, const TriMulW& w, bool outgoing);
 void launch_pair_transition(genie_ctx* h, hipStream_t st, const PairLayerW& w);
+void launch_triatt(genie_ctx* h, hipStream_t st, const TriAttW& w, bool starting);       // p += tri_att_{start,end}(p)
+void triatt_ws_floats(const genie_dims_t& d, int B, int N, size_t* tb, size_t* xn, size_t* qkvg);   // sizes of ta_tb, ta_xn, ta_qkvg
 bool launch_pair_stack_fused(genie_ctx* h, hipStream_t st, float* tap_trimul_out0, float* tap_layer0);   // false: not applicable, use the launches above
 void launch_ipa_bias(genie_ctx* h, hipStream_t st);
 void launch_ipa_prep(genie_ctx* h, hipStream_t st, int b0 = 0, int nb = -1);       // batch entries b0 .. b0 + nb - 1 (nb < 0: all)

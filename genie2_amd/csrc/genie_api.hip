@@ -27,7 +27,8 @@ static char g_create_err[512] = "";
 static const char* kKernelNames[KC_COUNT] = {
     "single_input", "gemm_rows", "layernorm_rows", "pair_static", "pair_init", "trimul_proj", "trimul_contract",
     "trimul_out", "pair_transition", "ipa_bias", "ipa_prep", "ipa_attn", "bb_update", "struct_rows", "p_sample_frenet", "misc",
-    "pair_fused_a", "pair_fused_b", "train_gemm", "train_elementwise", "train_layernorm", "train_transpose", "train_ipa", "train_misc"};
+    "pair_fused_a", "pair_fused_b", "train_gemm", "train_elementwise", "train_layernorm", "train_transpose", "train_ipa", "train_misc",
+    "tri_att_proj", "tri_att_core", "tri_att_transpose"};
 
 // ------------------------------------------------------------------ profiling
 void prof_begin(genie_ctx* h, hipStream_t st, int cls) {
@@ -62,6 +63,10 @@ static const char* check_dims(const genie_dims_t& d) {
     if (d.pair_transition_n < 1 || d.n_timestep < 1 || d.relpos_k < 0) return "bad dims";
     if (d.n_structure_layer < 1 || d.n_structure_block < 1 || d.n_pair_transform_layer < 0) return "bad layer counts";
     if ((d.n_head_ipa * d.c_hidden_ipa) % 4 || ipa_cat_n(d) % 4 || ipa_proj_n(d) % 4) return "IPA widths must be multiples of 4";
+    // triangular attention (n_head_tri == 0: none): the core kernel is built for head widths 16 and 32 with H c == c_p == 128
+    if (d.n_head_tri < 0) return "n_head_tri must be >= 0";
+    if (d.n_head_tri > 0 && d.c_hidden_tri_att != 16 && d.c_hidden_tri_att != 32) return "c_hidden_tri_att must be 16 or 32";
+    if (d.n_head_tri > 0 && d.n_head_tri * d.c_hidden_tri_att != 128) return "n_head_tri * c_hidden_tri_att must be 128 (4 heads of 32 or 8 of 16)";
     return nullptr;
 }
 
@@ -73,7 +78,9 @@ size_t genie_weight_count(const genie_dims_t* dp) {
     n += 2 * cp * cs + cp * (2 * d.relpos_k + 3) + cp * (d.template_dist_n_bin + 6) + cp * (d.template_dist_n_bin + 2);
     const size_t tm = 4 * (ch * cp + ch) + (cp * cp + cp) + (cp * ch + cp) + 2 * cp + 2 * ch;
     const size_t pt = 2 * cp + (d.pair_transition_n * cp * cp + d.pair_transition_n * cp) + (cp * d.pair_transition_n * cp + cp);
-    n += (size_t)d.n_pair_transform_layer * (2 * tm + pt);
+    const size_t hc = (size_t)d.n_head_tri * d.c_hidden_tri_att;
+    const size_t ta = d.n_head_tri > 0 ? 2 * cp + d.n_head_tri * cp + 3 * hc * cp + (cp * hc + cp) + (hc * cp + hc) : 0;   // one TriangleAttention
+    n += (size_t)d.n_pair_transform_layer * (2 * tm + 2 * ta + pt);
     const size_t H = d.n_head_ipa, C = d.c_hidden_ipa, Pq = d.n_qk_point, Pv = d.n_v_point;
     size_t sl = H;
     sl += (H * C) * cs + H * C + (2 * H * C) * cs + 2 * H * C + (3 * H * Pq) * cs + 3 * H * Pq + (3 * H * (Pq + Pv)) * cs + 3 * H * (Pq + Pv);
@@ -378,6 +385,31 @@ int genie_load_weights(genie_handle_t h, const float* blob, size_t n_floats) {
             slot(&T.ln_in_g, ones_off); slot(&T.ln_in_b, zeros_off);
             slot(&T.ln_out_g, ones_off); slot(&T.ln_out_b, zeros_off);
         }
+        for (int node = 0; node < (d.n_head_tri > 0 ? 2 : 0); ++node) {     // tri_att_start, tri_att_end (pair_triatt_kernels.hip)
+            TriAttW& A = node == 0 ? L.ta_start : L.ta_end;
+            const size_t hc = (size_t)d.n_head_tri * d.c_hidden_tri_att;
+            const float* ln_g = c.take(cp); const float* ln_b = c.take(cp);
+            const float* b_w = c.take(d.n_head_tri * cp);
+            const float* q_w = c.take(hc * cp); const float* k_w = c.take(hc * cp); const float* v_w = c.take(hc * cp);
+            const float* o_w = c.take(cp * hc); const float* o_b = c.take(cp);
+            const float* g_w = c.take(hc * cp); const float* g_b = c.take(hc);
+            if (!g_b) { SET_ERR(h, "genie_load_weights: blob too short"); return GENIE_E_ARG; }
+            slot(&A.ln_g, img.raw(ln_g, cp)); slot(&A.ln_b, img.raw(ln_b, cp));
+            slot(&A.wb, img.raw(b_w, d.n_head_tri * cp));
+            auto w = vcat({{q_w, hc * cp}, {k_w, hc * cp}, {v_w, hc * cp}, {g_w, hc * cp}});
+            std::vector<float> bv(4 * hc, 0.f);
+            memcpy(&bv[3 * hc], g_b, hc * sizeof(float));
+            pack_gemm(&A.proj_w, w.data(), (int)(4 * hc), (int)cp);
+            slot(&A.proj_b, img.raw(bv.data(), bv.size()));
+            pack_gemm(&A.out_w, o_w, (int)cp, (int)hc); slot(&A.out_b, img.raw(o_b, cp));
+            // f16 split scales of the core's q, k, v: |W (g xhat + beta)| <= |W diag g|_2 sqrt(c_p) + |W beta| per output row
+            auto scale_of = [&](const float* W) {
+                std::vector<float> wf(W, W + hc * cp), bf(hc, 0.f);
+                fold_ln(wf, bf, (int)hc, (int)cp, ln_g, ln_b);
+                return p2floor(32768.0 / hx_bound(wf.data(), bf.data(), (int)hc, (int)cp));
+            };
+            A.sq = scale_of(q_w); A.sk = scale_of(k_w); A.sv = scale_of(v_w);
+        }
         const size_t nh = (size_t)d.pair_transition_n * cp;
         const float* lg = c.take(cp); const float* lb = c.take(cp);
         const float* w1 = c.take(nh * cp); const float* b1 = c.take(nh);
@@ -498,8 +530,9 @@ int genie_load_weights(genie_handle_t h, const float* blob, size_t n_floats) {
     HIP_TRY(h, hipMemcpy(h->hxdev, hx.d.data(), hx.d.size() * 2, hipMemcpyHostToDevice));
     for (auto& f : hxfix) *f.first = h->hxdev + f.second;
     h->n_hxg = 0;
-    for (auto& g : gfix)
-        if (h->n_hxg < 64) h->hxg[h->n_hxg++] = HxGemmW{*g.slot, h->hxdev + g.hx_off, g.inv_s};
+    const int hxg_cap = (int)(sizeof(h->hxg) / sizeof(h->hxg[0]));
+    if ((int)gfix.size() > hxg_cap) { SET_ERR(h, "genie_load_weights: %zu row-GEMM weights exceed the %d hx image slots", gfix.size(), hxg_cap); return GENIE_E_ARG; }
+    for (auto& g : gfix) h->hxg[h->n_hxg++] = HxGemmW{*g.slot, h->hxdev + g.hx_off, g.inv_s};
     h->have_weights = true;
     return GENIE_OK;
 }
@@ -576,6 +609,11 @@ int genie_prepare_features(genie_handle_t h, genie_stream_t stream, int B, int N
     want(&h->tsteps, (size_t)B * 4); want(&h->rmaskf, M * 4); want(&h->pmax, 4); want(&h->spart, 3 * M * cs * 4);      // SR_KSPLIT slices
     want(&h->f_aatype, M * 20 * 4); want(&h->f_rmask, M * 4); want(&h->f_ridx, M * 4); want(&h->f_cidx, M * 4);
     want(&h->f_pos, M * 3 * 4); want(&h->f_fsm, M); want(&h->f_fstm, P); want(&h->f_ifm, M);
+    if (d.n_head_tri > 0) {     // triangular attention: the bias of one module and one slab's LayerNorm output and q|k|v|g (appended: nothing moves without it)
+        size_t ntb, nxn, nq;
+        triatt_ws_floats(d, B, N, &ntb, &nxn, &nq);
+        want(&h->ta_tb, ntb * 4); want(&h->ta_xn, nxn * 4); want(&h->ta_qkvg, nq * 4);
+    }
     size_t total = 0;
     for (auto& s : segs) total += s.bytes;
     if (total > h->ws_bytes) {
@@ -642,11 +680,17 @@ static int denoise_internal(genie_ctx* h, hipStream_t st, const float* trans, co
     if (taps && taps->p_init) HIP_TRY(h, d2d(taps->p_init, h->p, P * cp * 4));
 
     // pair transform net
+    // (with triangular attention the fused chains decline: its two modules sit between the incoming multiplication and the transition)
     const bool fused = launch_pair_stack_fused(h, st, taps ? taps->p_trimul_out0 : nullptr, taps ? taps->p_layer0 : nullptr);
     for (int l = 0; l < (fused ? 0 : d.n_pair_transform_layer); ++l) {
         launch_trimul(h, st, h->pair[l].out, true);
         if (l == 0 && taps && taps->p_trimul_out0) HIP_TRY(h, d2d(taps->p_trimul_out0, h->p, P * cp * 4));
         launch_trimul(h, st, h->pair[l].in, false);
+        if (d.n_head_tri > 0) {
+            launch_triatt(h, st, h->pair[l].ta_start, true);
+            launch_triatt(h, st, h->pair[l].ta_end, false);
+            if (l == 0 && taps && taps->p_tri_att0) HIP_TRY(h, d2d(taps->p_tri_att0, h->p, P * cp * 4));
+        }
         launch_pair_transition(h, st, h->pair[l]);
         if (l == 0 && taps && taps->p_layer0) HIP_TRY(h, d2d(taps->p_layer0, h->p, P * cp * 4));
     }

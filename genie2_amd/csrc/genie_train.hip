@@ -782,6 +782,7 @@ int genie_train_forward_backward(genie_handle_t h, genie_stream_t stream, const 
     if (!h) return GENIE_E_ARG;
     if (!h->have_tables || !h->have_feats) { TR_ERR("genie_train_forward_backward: call genie_set_tables and genie_prepare_features first"); return GENIE_E_STATE; }
     if (!weights || !grads || !trans || !rots || !timesteps || !z_target || !opts || !losses_out) { TR_ERR("genie_train_forward_backward: null argument"); return GENIE_E_ARG; }
+    if (h->d.n_head_tri > 0) { TR_ERR("genie_train_forward_backward: triangular attention has no backward pass here (sampling only)"); return GENIE_E_ARG; }
     if (h->d.c_s > 512 || h->d.c_p > 512 || h->d.c_hidden_mul > 512) { TR_ERR("training path: channel widths above 512 are not supported"); return GENIE_E_ARG; }
     if (hipSetDevice(h->device) != hipSuccess) return GENIE_E_HIP;
     hipStream_t st = (hipStream_t)stream;
@@ -817,6 +818,7 @@ int genie_denoise_vjp(genie_handle_t h, genie_stream_t stream, const float* weig
     if (!h) return GENIE_E_ARG;
     if (!h->have_tables || !h->have_feats) { TR_ERR("genie_denoise_vjp: call genie_set_tables and genie_prepare_features first"); return GENIE_E_STATE; }
     if (!weights || !trans || !rots || !timesteps || !dz || !dtrans_out) { TR_ERR("genie_denoise_vjp: null argument"); return GENIE_E_ARG; }
+    if (h->d.n_head_tri > 0) { TR_ERR("genie_denoise_vjp: triangular attention has no backward pass here (sampling only)"); return GENIE_E_ARG; }
     if (hipSetDevice(h->device) != hipSuccess) return GENIE_E_HIP;
     hipStream_t st = (hipStream_t)stream;
     genie_train_opts_t opt{};

@@ -815,6 +815,7 @@ void launch_pair_fused(genie_ctx* h, hipStream_t st, const HxFusedW& f, const Hx
 bool launch_pair_stack_fused(genie_ctx* h, hipStream_t st, float* tap_trimul_out0, float* tap_layer0) {
     const int L = h->d.n_pair_transform_layer;
     if (!h->hx || L < 1 || getenv("GENIE_NO_PAIR_FUSE")) return false;
+    if (h->d.n_head_tri > 0) return false;       // triangular attention sits inside chain B's span: the separate launches carry it
     const size_t pbytes = (size_t)h->B * h->N * h->N * h->d.c_p * 4;
     hx_trimul_proj(h, st, h->pair[0].out, true);
     for (int l = 0; l < L; ++l) {

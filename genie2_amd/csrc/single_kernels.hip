@@ -1727,8 +1727,8 @@ void launch_single_input(genie_ctx* h, hipStream_t st, const int32_t* timesteps)
 }
 
 void launch_gemm_rows(genie_ctx* h, hipStream_t st, const float* A, int lda, int M, int K, const float* Wp, int Nout,
-                      const float* bias, const float* res, int ldr, const float* rowmask, int relu, float* out, int ldo) {
-    ProfScope ps(h, st, KC_GEMM_ROWS);
+                      const float* bias, const float* res, int ldr, const float* rowmask, int relu, float* out, int ldo, int prof_class) {
+    ProfScope ps(h, st, prof_class);
     dim3 grid((M + 31) / 32, (Nout + 127) / 128);
     if (h->hx) {
         for (int i = 0; i < h->n_hxg; ++i)

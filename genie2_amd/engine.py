@@ -56,7 +56,7 @@ class GenieEngine:
             raise capi.GenieError('GenieEngine needs a GPU device (there is no CPU path)')
         if not torch.cuda.is_available():
             raise capi.GenieError('no HIP device visible to PyTorch')
-        self.dims = {k: dims[k] for k in pack.DIM_KEYS}
+        self.dims = pack.engine_dims(dims)          # DIM_KEYS + the triangular attention pair (0, 0 when the dict has none)
         cd = capi.GenieDims(**self.dims)
         self._h = C.c_void_p()
         rc = self.lib.genie_create(C.byref(cd), self.device.index or 0, C.byref(self._h))
@@ -191,7 +191,10 @@ class GenieEngine:
         return z, dt
 
     def denoise(self, trans, rots, timesteps, quat_codes=None, taps=()):
-        """Denoiser.forward.  Returns {'z': ..., <tap>: ...}."""
+        """Denoiser.forward.  Returns {'z': ..., <tap>: ...}.  'p_tri_att0' (p after layer 0's ending-node triangular
+        attention) exists only on an engine with n_head_tri > 0."""
+        if 'p_tri_att0' in taps and not self.dims['n_head_tri']:
+            raise capi.GenieError('tap p_tri_att0 needs a model with triangular attention')
         B, N = self.B, self.N
         trans = self._dev(trans, torch.float32)
         rots = self._dev(rots, torch.float32)
@@ -201,6 +204,7 @@ class GenieEngine:
         shapes = {'s': (B, N, self.dims['c_s']), 'p': (B, N, N, self.dims['c_p']), 's_final': (B, N, self.dims['c_s']),
                   'rots_out': (B, N, 3, 3), 'trans_out': (B, N, 3), 'p_init': (B, N, N, self.dims['c_p']),
                   'p_layer0': (B, N, N, self.dims['c_p']), 'p_trimul_out0': (B, N, N, self.dims['c_p']),
+                  'p_tri_att0': (B, N, N, self.dims['c_p']),
                   'ipa_cat0': (B, N, self.dims['n_head_ipa'] * (self.dims['c_hidden_ipa'] + 4 * self.dims['n_v_point'] + self.dims['c_p'])),
                   'states': (1 + self.dims['n_structure_block'] * self.dims['n_structure_layer'], B, N, self.dims['c_s'])}
         out = {k: torch.empty(shapes[k], device=self.device) for k in taps}

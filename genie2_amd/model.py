@@ -2,7 +2,9 @@
 
 Same constructor signature, same `state_dict()` keys and shapes (so reference
 checkpoints load unchanged), same call `model(ts, timesteps, features)['z']`
--- but `forward` is one call into libgenie_hip.so.  It is inference only
+-- but `forward` is one call into libgenie_hip.so.  `include_tri_att=True` adds the
+reference's tri_att_start / tri_att_end parameters to every pair transform layer and runs
+them (csrc/pair_triatt_kernels.hip).  It is inference only
 (no autograd through the HIP kernels) and has no CPU path: calling it on a CPU
 device raises.
 """
@@ -26,8 +28,6 @@ class Denoiser(nn.Module):
                  pair_transition_n, n_structure_layer, n_structure_block, c_hidden_ipa, n_head_ipa, n_qk_point, n_v_point,
                  ipa_dropout, n_structure_transition_layer, structure_transition_dropout):
         super().__init__()
-        if include_tri_att:
-            raise NotImplementedError('triangular attention is disabled in every Genie 2 config and is not built here')
         if not include_mul_update and n_pair_transform_layer > 0:
             raise NotImplementedError('pair transform layers without triangular multiplication are not supported')
         if n_structure_transition_layer != 1:
@@ -39,7 +39,11 @@ class Denoiser(nn.Module):
             template_dist_step=float(template_dist_step), n_pair_transform_layer=n_pair_transform_layer,
             c_hidden_mul=c_hidden_mul, pair_transition_n=pair_transition_n, n_structure_layer=n_structure_layer,
             n_structure_block=n_structure_block, c_hidden_ipa=c_hidden_ipa, n_head_ipa=n_head_ipa, n_qk_point=n_qk_point,
-            n_v_point=n_v_point, rescale=float(rescale), n_timestep=n_timestep, max_n_res=max_n_res, max_n_chain=max_n_chain)
+            n_v_point=n_v_point, rescale=float(rescale), n_timestep=n_timestep, max_n_res=max_n_res, max_n_chain=max_n_chain,
+            # triangular attention (sampling only: GenieTrainer and TwistedSampler refuse such a model)
+            c_hidden_tri_att=int(c_hidden_tri_att) if include_tri_att else 0, n_head_tri=int(n_head_tri) if include_tri_att else 0)
+        if include_tri_att and n_head_tri < 1:
+            raise ValueError('include_tri_att needs n_head_tri >= 1')
         init = pack.random_state_dict(self.dims, seed=0)
         for key, _ in pack.weight_layout(self.dims):
             *path, leaf = key.split('.')

@@ -15,6 +15,18 @@ DIM_KEYS = (
     'template_dist_min', 'template_dist_step', 'n_pair_transform_layer', 'c_hidden_mul', 'pair_transition_n',
     'n_structure_layer', 'n_structure_block', 'c_hidden_ipa', 'n_head_ipa', 'n_qk_point', 'n_v_point',
     'rescale', 'n_timestep', 'max_n_res', 'max_n_chain')
+# Triangular attention (include_tri_att): per-head width and number of heads.  They travel apart from DIM_KEYS, whose contents
+# are the frozen dims dict of the oracle; absent or n_head_tri == 0 means "no triangular attention".
+TRI_DIM_KEYS = ('c_hidden_tri_att', 'n_head_tri')
+
+
+def engine_dims(dims):
+    """The fields of genie_dims_t from a dims dict: DIM_KEYS as they are, TRI_DIM_KEYS defaulting to 0."""
+    out = {k: dims[k] for k in DIM_KEYS}
+    out.update({k: int(dims.get(k, 0) or 0) for k in TRI_DIM_KEYS})
+    if out['n_head_tri'] == 0:
+        out['c_hidden_tri_att'] = 0
+    return out
 
 
 def _linear(out, prefix, o, i, bias=True):
@@ -29,7 +41,8 @@ def _norm(out, prefix, c):
 
 
 def weight_layout(dims):
-    """Ordered [(key, shape)] of every Denoiser parameter."""
+    """Ordered [(key, shape)] of every Denoiser parameter (with dims['n_head_tri'] > 0: including the two triangular
+    attention modules of every pair transform layer, between tri_mul_in.* and pair_transition.* as in the reference)."""
     d = dims
     c_s, c_p, ch = d['c_s'], d['c_p'], d['c_hidden_mul']
     H, C, Pq, Pv = d['n_head_ipa'], d['c_hidden_ipa'], d['n_qk_point'], d['n_v_point']
@@ -52,6 +65,15 @@ def weight_layout(dims):
             _linear(lay, t + 'linear_z', c_p, ch)
             _norm(lay, t + 'layer_norm_in', c_p)
             _norm(lay, t + 'layer_norm_out', ch)
+        ht, ct = int(d.get('n_head_tri', 0) or 0), int(d.get('c_hidden_tri_att', 0) or 0)
+        for node in (('tri_att_start.', 'tri_att_end.') if ht > 0 else ()):       # triangular_attention.py:57-65, primitives.py:203-217
+            t = base + node
+            _norm(lay, t + 'layer_norm', c_p)
+            _linear(lay, t + 'linear', ht, c_p, False)
+            for name in ('linear_q', 'linear_k', 'linear_v'):
+                _linear(lay, t + 'mha.' + name, ht * ct, c_p, False)
+            _linear(lay, t + 'mha.linear_o', c_p, ht * ct)
+            _linear(lay, t + 'mha.linear_g', ht * ct, c_p)
         t = base + 'pair_transition.'
         _norm(lay, t + 'layer_norm', c_p)
         _linear(lay, t + 'linear_1', d['pair_transition_n'] * c_p, c_p)

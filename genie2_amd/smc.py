@@ -119,7 +119,13 @@ class TwistedSampler(UnconditionalSampler):
     or, instead, 'motif_target' (list of [n_i, 3] segments: the placements are enumerated with generate_motif_index_mask and the
     potential is motif_twisting_function over all of them, unconditional_smc.py:303-345); optional 'tausq' with it;
     optional 'noise' [T,B,N,3] (initial draw + one per step, as BaseSampler), 'resample_u' (list of uniforms, tests),
-    'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50)."""
+    'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50).
+    A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it."""
+
+    def __init__(self, model):
+        if getattr(model.model, 'dims', {}).get('n_head_tri', 0):       # before any device work
+            raise NotImplementedError('triangular attention: sampling only (the twisted sampler needs the denoiser VJP through it)')
+        super().__init__(model)
 
     def _sample(self, params):
         feats = F.convert_np_features_to_tensor(

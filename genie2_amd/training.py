@@ -59,6 +59,8 @@ class GenieTrainer:
     BETAS, EPS = (0.9, 0.999), 1e-8           # torch.optim.Adam defaults, as ddpm.py:73-77 leaves them
 
     def __init__(self, genie, backend=None, train_mode=True, fast_math=0, seed=None, force_overlap=False):
+        if genie.model.dims.get('n_head_tri', 0):       # before any device work: the attention has no backward pass
+            raise NotImplementedError('triangular attention: sampling only (the training backward pass through it is not built)')
         self.genie = genie
         self.config = genie.config
         self.dims = genie.model.dims

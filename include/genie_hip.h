@@ -53,6 +53,10 @@ typedef struct {
     int32_t c_hidden_ipa, n_head_ipa, n_qk_point, n_v_point;
     float   rescale;
     int32_t n_timestep, max_n_res, max_n_chain;
+    /* triangular attention of the pair stack (include_tri_att; genie/model/pair_transform_net.py:69-79): per-head width and
+     * number of heads.  n_head_tri == 0 (a zero-initialised tail): none, and c_hidden_tri_att is ignored.  Supported:
+     * (c_hidden_tri_att, n_head_tri) = (32, 4) and (16, 8); genie_create refuses anything else. */
+    int32_t c_hidden_tri_att, n_head_tri;
 } genie_dims_t;
 
 /* The tensors of the reference's 12-key feature dict the denoiser reads
@@ -83,11 +87,14 @@ typedef struct {
     float* states;     /* [1+blocks*layers,B,N,c_s] 'states' (structure_net.py:236-243) */
     float* p_trimul_out0; /* [B,N,N,c_p] p after layer 0's outgoing triangle multiplication (pair_transform_net.py:109-110; tap) */
     float* ipa_cat0;   /* [B,N,H*(c_hidden+4*Pv+c_p)] input of layer 0's IPA linear_out (invariant_point_attention.py:251-258; tap) */
+    float* p_tri_att0; /* [B,N,N,c_p] p after layer 0's ending-node triangular attention, before its pair transition
+                          (pair_transform_net.py:113-115; tap; written only with n_head_tri > 0; padded pairs hold free, finite values) */
 } genie_taps_t;
 
 /* ---- lifetime ---------------------------------------------------------- */
 
-/* Replaces Denoiser.__init__ (genie/model/model.py:20-123). */
+/* Replaces Denoiser.__init__ (genie/model/model.py:20-123).  Unsupported dims are refused with GENIE_E_ARG before the device is
+ * touched; genie_last_error(NULL) names the field. */
 int genie_create(const genie_dims_t* dims, int device, genie_handle_t* out);
 void genie_destroy(genie_handle_t h);
 const char* genie_last_error(genie_handle_t h);   /* h may be NULL: last create error */
@@ -99,7 +106,8 @@ size_t genie_weight_count(const genie_dims_t* dims);
  * Denoiser.state_dict() in its own order (checkpoint
  * keys are these with a 'model.' prefix, genie/utils/model_io.py:159-173),
  * each [out,in] row-major, concatenated.  Repacked into MFMA fragment order
- * and uploaded. */
+ * and uploaded.  With n_head_tri > 0 the tensors of tri_att_start and tri_att_end
+ * sit between tri_mul_in.* and pair_transition.* of every layer, as in the reference. */
 int genie_load_weights(genie_handle_t h, const float* blob, size_t n_floats);
 
 /* Sinusoidal tables and the diffusion schedule, computed by the host with
@@ -155,7 +163,9 @@ size_t genie_motif_potential_work_bytes(int B, int P);
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
  * (SURVEY.md hazard 1): 0 = canonical, else 1 + 2*m + neg = "component m has
- * sign (neg ? - : +)". */
+ * sign (neg ? - : +)".
+ * With n_head_tri > 0 every pair transform layer also runs the two triangular attention modules
+ * (csrc/pair_triatt_kernels.hip), in both arithmetic modes; so do genie_p_sample's and genie_sample_loop's calls. */
 int genie_denoise(genie_handle_t h, genie_stream_t stream,
                   const float* trans, const float* rots, const int32_t* timesteps,
                   const int8_t* quat_codes, float* z_out, const genie_taps_t* taps);
@@ -235,7 +245,9 @@ int genie_adam_step(genie_stream_t stream, size_t n, float* p, const float* g, f
  * fast_math: how the GEMMs' f32 operands reach the bf16 matrix pipe -- 0: split in three bf16 pieces (24 significand bits, six MFMAs
  * per product: f32-grade -- the reference's arithmetic, its Trainer sets no `precision=` (train.py:54-65) and trains in fp32; the
  * mode every parity test and every quoted figure uses), 2: two pieces (16 bits, three MFMAs), 1: plain bf16 operands (one MFMA;
- * what a bf16-autocast run would compute -- NARROWER than the reference, offered for BASELINE config 5's "bf16" wording only). */
+ * what a bf16-autocast run would compute -- NARROWER than the reference, offered for BASELINE config 5's "bf16" wording only).
+ * A handle with n_head_tri > 0 is refused with GENIE_E_ARG ("triangular attention: ..."): the backward pass through the
+ * attention is not built; the same holds for genie_denoise_vjp. */
 typedef struct {
     float tri_dropout, ipa_dropout, transition_dropout;
     uint32_t seed;
