@@ -1404,8 +1404,13 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
         auto step = [&](int it, float4 (&cur)[NBK][2], float4 (&nxt)[NBK][2]) {
             if (it + 1 < nit) fetch(it + 1, nxt);
             const int hh = hg * HL + it / nks, ki = it % nks, ks = ks0 + ki;
-            const bool live = ks * 32 + 8 * g < NP8;                              // att is zero padded up to NP8 only
-            const float* ap = ar + hh * NPA + (live ? ks * 32 : 0);
+            // att is zero padded up to NP8 only: a lane group beyond it takes scale 0 AND reads initialised memory (row 0, columns
+            // 0..7, written and softmaxed above since NP8 >= 8).  Columns NP8..NPA-1 of a row are never written, and a NaN or Inf
+            // left there by an earlier kernel times the scale 0 is a NaN in the matrix pipe.  The address used to fall back to
+            // column 8 g of the row (key step 0), which lies beyond NP8 only when NP8 < 32, i.e. N <= 24: longer structures never
+            // read the unwritten columns, and finite leftovers contribute 0.
+            const bool live = ks * 32 + 8 * g < NP8;
+            const float* ap = live ? ar + hh * NPA + ks * 32 : att;
             const float4 a0 = *reinterpret_cast<const float4*>(ap), a1 = *reinterpret_cast<const float4*>(ap + 4);
             const float xa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
             h8 ah, al;
@@ -1518,9 +1523,10 @@ __global__ __launch_bounds__(MF ? 128 * Q : 512, MF ? 4 : 1) void k_ipa_attn_q(c
                     for (int e = 0; e < 8; ++e)
                         nxt[e] = *reinterpret_cast<const float4*>(zr + (size_t)min(j0 + 32 + 8 * g + e, N - 1) * CP);
                 }
-                const bool live = j0 + 8 * g < NP8;                               // att is zero padded up to NP8 only
-                const float4 a0 = *reinterpret_cast<const float4*>(ar + (live ? j0 : 0));
-                const float4 a1 = *reinterpret_cast<const float4*>(ar + (live ? j0 : 0) + 4);
+                const bool live = j0 + 8 * g < NP8;                               // att is zero padded up to NP8 only (see above)
+                const float* ap = live ? ar + j0 : att;
+                const float4 a0 = *reinterpret_cast<const float4*>(ap);
+                const float4 a1 = *reinterpret_cast<const float4*>(ap + 4);
                 const float xa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
                 h8 ah, al;
                 hx_split8(xa, live ? sa : 0.0f, ah, al);

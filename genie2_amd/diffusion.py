@@ -75,18 +75,24 @@ def load_config(rootdir, name):
     return Config(os.path.join(rootdir, name, 'configuration'))
 
 
-def load_default_model(rootdir, name):
-    return Genie(load_config(rootdir, name))
+def load_default_model(rootdir, name, seed=None):
+    """model_io.py:64-77.  With a `seed` the untrained model carries the reference's initialisation for it
+    (Denoiser.init_reference_); without, the constructor's fixed default weights."""
+    genie = Genie(load_config(rootdir, name))
+    if seed is not None:
+        genie.model.init_reference_(seed)
+    return genie
 
 
-def load_model(rootdir, name, version=None, epoch=None):
-    """model_io.py:84-137: latest version / epoch by default; an untrained Genie when there is no checkpoint."""
+def load_model(rootdir, name, version=None, epoch=None, seed=None):
+    """model_io.py:84-137: latest version / epoch by default; an untrained Genie when there is no checkpoint (`seed` as in
+    load_default_model; a checkpoint's weights do not depend on it)."""
     versions = get_versions(rootdir, name)
     if version is None:
         if not versions:
             print('No checkpoint available (version)')
             print('Using default untrained model')
-            return load_default_model(rootdir, name)
+            return load_default_model(rootdir, name, seed)
         version = max(versions)
     else:
         assert version in versions, 'Missing checkpoint version: {}'.format(version)
@@ -95,7 +101,7 @@ def load_model(rootdir, name, version=None, epoch=None):
         if not epochs:
             print('No checkpoint available (epoch)')
             print('Using default untrained model')
-            return load_default_model(rootdir, name)
+            return load_default_model(rootdir, name, seed)
         epoch = max(epochs)
     else:
         assert epoch in epochs, 'Missing checkpoint epoch: {}'.format(epoch)

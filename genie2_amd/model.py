@@ -65,6 +65,17 @@ class Denoiser(nn.Module):
         self._drop_engine()
         return super().load_state_dict(*a, **k)
 
+    def init_reference_(self, seed):
+        """Overwrite every parameter, in place, with the reference's own initialisation for `seed`
+        (pack.reference_state_dict: what its Denoiser holds when built right after seed_everything(seed)).  The constructor's
+        default stays pack.random_state_dict(seed 0), the 'everything live' weights benchmarks and tests run on."""
+        self._drop_engine()
+        init = pack.reference_state_dict(self.dims, seed)
+        with torch.no_grad():
+            for key, p in self.named_parameters():
+                p.copy_(init[key])
+        return self
+
     def _drop_engine(self):
         if getattr(self, '_engine', None) is not None:
             self._engine.close()

@@ -176,6 +176,89 @@ def random_state_dict(dims, seed=0):
     return sd
 
 
+SOFTPLUS_INVERSE_1 = 0.541324854612918          # ipa.head_weights (primitives.py:90-93)
+
+
+def reference_init_mode(key):
+    """How the reference's modules initialise the tensor `key` (primitives.py:96-160,203-217,
+    triangular_attention.py:57-65): 'torch' (plain nn.Linear), 'lecun', 'relu', 'glorot', 'normal', 'gating', 'final' for a
+    Linear (weight and bias alike), 'norm' for a LayerNorm, 'head_weights'."""
+    *path, leaf = key.split('.')
+    name = path[-1]
+    if leaf == 'head_weights':
+        return 'head_weights'
+    if 'layer_norm' in name:
+        return 'norm'
+    if path[0] in ('single_feature_net', 'pair_feature_net'):
+        return 'torch'
+    if name in ('linear_a_g', 'linear_b_g', 'linear_g'):
+        return 'gating'
+    if name == 'linear_1' or (name == 'linear_2' and 'transition' in path):       # structure_transition.py:28-29, pair_transition.py:44
+        return 'relu'
+    if name in ('linear_z', 'linear_2', 'linear_3', 'linear_out', 'linear_o'):
+        return 'final'
+    if path[-2] == 'mha':                                   # linear_q / linear_k / linear_v of the triangular attention
+        return 'glorot'
+    if path[-2] in ('tri_att_start', 'tri_att_end'):        # the triangle bias projection
+        return 'normal'
+    return 'lecun'
+
+
+def reference_state_dict(dims, seed):
+    """The reference's own parameter initialisation: equal bit for bit to `state_dict()` of its `Denoiser(**config.model, ...)`
+    built right after `random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)` (genie/train.py:42,51,
+    genie/utils/model_io.py:64-77), in `weight_layout` order, float32.
+
+    Two private streams, consumed in the reference's construction order (which is the layout's order; head_weights is a
+    constant): `np.random.RandomState(seed)` feeds scipy's truncated normal of the lecun / He matrices (primitives.py:50-69,
+    with its fan computation as written: fan = out * in * out), `torch.Generator().manual_seed(seed)` feeds the plain
+    nn.Linear's of the two feature nets, the glorot / normal matrices of the triangular attention -- and the default
+    nn.Linear init that every primitives.Linear draws and then overwrites (primitives.py:135), replayed here on scratch
+    tensors so that later torch draws see the stream where the reference leaves it.  The global random / numpy / torch
+    states are neither read nor advanced."""
+    try:
+        import numpy as np
+        from scipy.stats import truncnorm
+    except ImportError as e:
+        raise ImportError('pack.reference_state_dict needs scipy (the reference draws its truncated normals with '
+                          'scipy.stats.truncnorm); install scipy or start from a checkpoint') from e
+    from torch.nn import init
+    rs = np.random.RandomState(seed)
+    g = torch.Generator().manual_seed(seed)
+    trunc_std = truncnorm.std(a=-2, b=2, loc=0, scale=1)
+    layout = weight_layout(dims)
+    has_bias = {k[:-len('.bias')] for k, _ in layout if k.endswith('.bias')}
+    sd = {}
+    for key, shape in layout:
+        mode = reference_init_mode(key)
+        if mode == 'head_weights':
+            sd[key] = torch.full(shape, SOFTPLUS_INVERSE_1, dtype=torch.float32)
+        elif mode == 'norm':
+            sd[key] = torch.ones(shape) if key.endswith('.weight') else torch.zeros(shape)
+        elif key.endswith('.bias'):                         # drawn with its weight, below
+            sd[key] = torch.full(shape, 1.0 if mode == 'gating' else 0.0, dtype=torch.float32)
+        else:
+            w = torch.empty(shape, dtype=torch.float32)
+            init.kaiming_uniform_(w, a=math.sqrt(5), generator=g)          # nn.Linear.reset_parameters
+            if key[:-len('.weight')] in has_bias:
+                bound = 1 / math.sqrt(shape[1])
+                init.uniform_(torch.empty(shape[0]), -bound, bound, generator=g)
+            if mode in ('lecun', 'relu'):
+                fan = shape[0] * shape[1] * shape[0]        # _calculate_fan (primitives.py:31-47) on an [out, in] matrix
+                std = math.sqrt((2.0 if mode == 'relu' else 1.0) / max(1, fan)) / trunc_std
+                samples = truncnorm.rvs(a=-2, b=2, loc=0, scale=std, size=shape[0] * shape[1], random_state=rs)
+                w.copy_(torch.tensor(np.reshape(samples, shape)))
+            elif mode == 'glorot':
+                init.xavier_uniform_(w, gain=1, generator=g)
+            elif mode == 'normal':
+                init.kaiming_normal_(w, nonlinearity='linear', generator=g)
+            elif mode in ('gating', 'final'):
+                w.zero_()
+            sd[key] = w
+        sd[key] = sd[key].contiguous()
+    return sd
+
+
 BASE_DIMS = dict(
     c_s=384, c_p=128, rescale=1.0, c_pos_emb=256, c_chain_emb=64, c_timestep_emb=512,
     relpos_k=32, template_dist_min=2.0, template_dist_step=0.5, template_dist_n_bin=37,

@@ -22,6 +22,22 @@ from .diffusion import get_versions, load_model, save_checkpoint
 from .training import GenieTrainer, format_log
 
 
+def build_model(config, weights_only=False):
+    """The model `main` trains (on the CPU; needs no GPU): the latest checkpoint under <rootdir>/<name> when there is one, with what
+    GenieTrainer.resume continues from in `.checkpoint_info` (dropped under `weights_only`); otherwise an untrained model at the
+    reference's initialisation for config.training['seed'] (pack.reference_state_dict), as the reference's seed_everything +
+    load_default_model give it.  Every rank computes the same weights from the seed: no broadcast."""
+    seed = config.training['seed']
+    model = load_model(config.io['rootdir'], config.io['name'], seed=seed)
+    if getattr(model, 'checkpoint_info', None) is None:
+        if int(os.environ.get('RANK', 0)) == 0:
+            print('Initialised from scratch: reference scheme (lecun / He truncated normal, zero final layers, unit gate biases), '
+                  'seed {}'.format(seed))
+    elif weights_only:
+        model.checkpoint_info = {}
+    return model
+
+
 def main(args):
     config = Config(filename=args.config)
     world, rank, local = int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('RANK', 0)), int(os.environ.get('LOCAL_RANK', 0))
@@ -36,10 +52,10 @@ def main(args):
         dm.setup()
     if ddp:
         td.barrier()
-    model = load_model(config.io['rootdir'], config.io['name']).to(f'cuda:{local}')
+    model = build_model(config, args.weights_only).to(f'cuda:{local}')
     trainer = GenieTrainer(model, force_overlap=args.force_overlap)
     info = getattr(model, 'checkpoint_info', None)
-    if info and not args.weights_only:
+    if info:
         trainer.resume(info)
         if rank == 0:
             print('Resuming at epoch {} (Adam step {})'.format(trainer.epoch, trainer.step))
