@@ -94,6 +94,10 @@ SYMBOLS = {
     'genie_motif_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     'genie_motif_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'genie_motif_potential_rigid': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t]),
+    'genie_motif_potential_rigid_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 _lib = None

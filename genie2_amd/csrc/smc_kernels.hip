@@ -250,6 +250,321 @@ __global__ __launch_bounds__(MP_THREADS) void k_motif_potential(const float* __r
     }
 }
 
+// ---- the superposed (rigid) form: genie_motif_potential_rigid ---------------------------------------------------------------------
+// Every placement is compared to the motif in its best-fitting orientation.  With t_c = target - mean(target):
+//   R_bp = argmin over proper rotations of sum_m |c_bp(m) - R t_c(m)|^2,   e_bp(m) = c_bp(m) - R_bp t_c(m),   q_bp = sum_m |e_bp(m)|^2
+//   score[b,p] = -q_bp / (2 var),   logp[b] = logsumexp_p score[b,p] - log P,   grad[b,n] = -sum_p w_bp [n in p] e_bp(m_p(n)) / var
+// (the derivative through R vanishes at the optimum, and sum_m e = 0 because both sides are centred), best[b] = the lowest p with the
+// largest score, rmsd[b] = sqrt(q_{b,best} / M).  R is Horn's quaternion: the eigenvector of the largest eigenvalue of the symmetric
+// 4x4 matrix built from the correlation sum_m t_c c^T, found by MR_SWEEPS cyclic Jacobi sweeps in float32 with the matrix and the
+// eigenvectors in named registers (a quaternion is always a proper rotation: a mirror image does not fit).  q is then summed from the
+// residuals with R applied, never as G_x + G_t - 2 lambda, which cancels to nothing exactly when the fit is good.  A collinear
+// selection has a double largest eigenvalue: Jacobi still returns one unit eigenvector of it, the score is the same for all of them.
+//
+// Layout as above with a record (q, centroid, quaternion) of 32 B per placement, MR_LDS_P of them in LDS; the gather rebuilds R from
+// the quaternion (wave-uniform).  Without a gradient to write, one work-group per particle does the scoring and the gather is skipped.
+constexpr int MR_LDS_P = 1024;          // placement records (32 B each) kept in LDS; more spill to `work`
+constexpr int MR_SWEEPS = 6;            // cyclic Jacobi sweeps of the 4x4 (quadratic convergence: 4 reach float32 on these matrices)
+
+// one Jacobi rotation in the (p, q) plane: a_pq -> 0.  (a1p, a1q), (a2p, a2q): the two other rows' entries in columns p and q;
+// v*p, v*q: columns p and q of the eigenvector matrix.  (The fit is plain arithmetic, __host__ too: it can be run on the CPU
+// against a float64 fit.)
+__host__ __device__ __forceinline__ void mr_mix(float& x, float& y, float s, float tau) {
+    const float g = x, h = y;
+    x = g - s * (h + tau * g);
+    y = h + s * (g - tau * h);
+}
+
+__host__ __device__ __forceinline__ void mr_rot(float& app, float& aqq, float& apq, float& a1p, float& a1q, float& a2p, float& a2q,
+                                                float& v0p, float& v0q, float& v1p, float& v1q, float& v2p, float& v2q, float& v3p,
+                                                float& v3q) {
+    const float th = (aqq - app) / (2.f * apq);
+    float t = copysignf(1.f, th) / (fabsf(th) + sqrtf(th * th + 1.f));      // (th = +-inf gives 0)
+    t = apq == 0.f ? 0.f : t;                                               // (and th = 0/0 is never used)
+    const float c = 1.f / sqrtf(t * t + 1.f), s = t * c, tau = s / (1.f + c), h = t * apq;
+    app -= h;
+    aqq += h;
+    apq = 0.f;
+    mr_mix(a1p, a1q, s, tau);
+    mr_mix(a2p, a2q, s, tau);
+    mr_mix(v0p, v0q, s, tau);
+    mr_mix(v1p, v1q, s, tau);
+    mr_mix(v2p, v2q, s, tau);
+    mr_mix(v3p, v3q, s, tau);
+}
+
+// Horn (1987): the unit quaternion (w, x, y, z) of the proper rotation R that maximises sum_m (R t(m)) . c(m), from S_ab = sum_m t_a c_b
+__host__ __device__ __forceinline__ float4 mr_quaternion(float Sxx, float Sxy, float Sxz, float Syx, float Syy, float Syz, float Szx,
+                                                         float Szy, float Szz) {
+    float a00 = Sxx + Syy + Szz, a01 = Syz - Szy, a02 = Szx - Sxz, a03 = Sxy - Syx;
+    float a11 = Sxx - Syy - Szz, a12 = Sxy + Syx, a13 = Szx + Sxz;
+    float a22 = -Sxx + Syy - Szz, a23 = Syz + Szy;
+    float a33 = -Sxx - Syy + Szz;
+    float v00 = 1.f, v01 = 0.f, v02 = 0.f, v03 = 0.f, v10 = 0.f, v11 = 1.f, v12 = 0.f, v13 = 0.f;
+    float v20 = 0.f, v21 = 0.f, v22 = 1.f, v23 = 0.f, v30 = 0.f, v31 = 0.f, v32 = 0.f, v33 = 1.f;
+#pragma unroll
+    for (int sweep = 0; sweep < MR_SWEEPS; ++sweep) {
+        mr_rot(a00, a11, a01, a02, a12, a03, a13, v00, v01, v10, v11, v20, v21, v30, v31);
+        mr_rot(a00, a22, a02, a01, a12, a03, a23, v00, v02, v10, v12, v20, v22, v30, v32);
+        mr_rot(a00, a33, a03, a01, a13, a02, a23, v00, v03, v10, v13, v20, v23, v30, v33);
+        mr_rot(a11, a22, a12, a01, a02, a13, a23, v01, v02, v11, v12, v21, v22, v31, v32);
+        mr_rot(a11, a33, a13, a01, a03, a12, a23, v01, v03, v11, v13, v21, v23, v31, v33);
+        mr_rot(a22, a33, a23, a02, a03, a12, a13, v02, v03, v12, v13, v22, v23, v32, v33);
+    }
+    // the column of the largest eigenvalue (the first of equal ones), by selects between named values: an index into the columns
+    // would put them in scratch
+    const bool b1 = a11 > a00;
+    const float l1 = b1 ? a11 : a00;
+    const bool b2 = a22 > l1;
+    const float l2 = b2 ? a22 : l1;
+    const bool b3 = a33 > l2;
+    const float w = b3 ? v03 : b2 ? v02 : b1 ? v01 : v00, x = b3 ? v13 : b2 ? v12 : b1 ? v11 : v10;
+    const float y = b3 ? v23 : b2 ? v22 : b1 ? v21 : v20, z = b3 ? v33 : b2 ? v32 : b1 ? v31 : v30;
+    const float r = 1.f / sqrtf(w * w + x * x + y * y + z * z);             // (the columns stay orthonormal to rounding)
+    return make_float4(w * r, x * r, y * r, z * r);
+}
+
+struct MrRot {
+    float xx, xy, xz, yx, yy, yz, zx, zy, zz;
+};
+
+__host__ __device__ __forceinline__ MrRot mr_rotation(float4 q) {
+    const float w = q.x, x = q.y, y = q.z, z = q.w;
+    MrRot R;
+    R.xx = 1.f - 2.f * (y * y + z * z);
+    R.xy = 2.f * (x * y - w * z);
+    R.xz = 2.f * (x * z + w * y);
+    R.yx = 2.f * (x * y + w * z);
+    R.yy = 1.f - 2.f * (x * x + z * z);
+    R.yz = 2.f * (y * z - w * x);
+    R.zx = 2.f * (x * z - w * y);
+    R.zy = 2.f * (y * z + w * x);
+    R.zz = 1.f - 2.f * (x * x + y * y);
+    return R;
+}
+
+struct MrRec {
+    float4 fit;             // (q, centroid)
+    float4 quat;            // (w, x, y, z)
+};
+
+// (q, centroid) and the quaternion of one placement; (tbx, tby, tbz) = mean(target)
+__host__ __device__ __forceinline__ MrRec mr_record(const MpLds& L, const int32_t* __restrict__ st, int S, int M, float tbx, float tby,
+                                                    float tbz) {
+    float cx = 0.f, cy = 0.f, cz = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const int r0 = st[s], n = L.sl[s];
+        for (int i = 0; i < n; ++i) {
+            const float* x = L.xs + 3 * (r0 + i);
+            cx += x[0];
+            cy += x[1];
+            cz += x[2];
+        }
+    }
+    cx /= (float)M;
+    cy /= (float)M;
+    cz /= (float)M;
+    float Sxx = 0.f, Sxy = 0.f, Sxz = 0.f, Syx = 0.f, Syy = 0.f, Syz = 0.f, Szx = 0.f, Szy = 0.f, Szz = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const int r0 = st[s], n = L.sl[s], m0 = L.so[s];
+        for (int i = 0; i < n; ++i) {
+            const float* x = L.xs + 3 * (r0 + i);
+            const float* t = L.tg + 3 * (m0 + i);
+            const float ux = x[0] - cx, uy = x[1] - cy, uz = x[2] - cz, tx = t[0] - tbx, ty = t[1] - tby, tz = t[2] - tbz;
+            Sxx += tx * ux;
+            Sxy += tx * uy;
+            Sxz += tx * uz;
+            Syx += ty * ux;
+            Syy += ty * uy;
+            Syz += ty * uz;
+            Szx += tz * ux;
+            Szy += tz * uy;
+            Szz += tz * uz;
+        }
+    }
+    const float4 qt = mr_quaternion(Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz);
+    const MrRot R = mr_rotation(qt);
+    float q = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const int r0 = st[s], n = L.sl[s], m0 = L.so[s];
+        for (int i = 0; i < n; ++i) {
+            const float* x = L.xs + 3 * (r0 + i);
+            const float* t = L.tg + 3 * (m0 + i);
+            const float tx = t[0] - tbx, ty = t[1] - tby, tz = t[2] - tbz;
+            const float ex = (x[0] - cx) - (R.xx * tx + R.xy * ty + R.xz * tz);
+            const float ey = (x[1] - cy) - (R.yx * tx + R.yy * ty + R.yz * tz);
+            const float ez = (x[2] - cz) - (R.zx * tx + R.zy * ty + R.zz * tz);
+            q += ex * ex + ey * ey + ez * ez;
+        }
+    }
+    return MrRec{make_float4(q, cx, cy, cz), qt};
+}
+
+__device__ inline void mr_target_mean(const MpLds& L, int M, float& tbx, float& tby, float& tbz) {
+    tbx = tby = tbz = 0.f;
+    for (int m = 0; m < M; ++m) {
+        tbx += L.tg[3 * m];
+        tby += L.tg[3 * m + 1];
+        tbz += L.tg[3 * m + 2];
+    }
+    tbx /= (float)M;
+    tby /= (float)M;
+    tbz /= (float)M;
+}
+
+__device__ inline int mr_block_min(int v, int* slot) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int r = slot[0];
+    for (int w = 1; w < MP_WAVES; ++w) r = min(r, slot[w]);
+    return r;
+}
+
+// large-P path, first launch: one placement per thread, records to work[b, p, 0..1]
+__global__ __launch_bounds__(MP_THREADS) void k_motif_rigid_records(const float* __restrict__ x0, int N, int P, int S, int M,
+                                                                    const int32_t* __restrict__ seg_len,
+                                                                    const int32_t* __restrict__ starts, const float* __restrict__ target,
+                                                                    float4* __restrict__ work) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mp_smem[];
+    const int b = blockIdx.y;
+    const MpLds L = mp_carve(mp_smem, N, M, S, 0);          // (act / wcnt unused here)
+    mp_stage(L, x0 + (size_t)b * 3 * N, target, seg_len, N, M, S);
+    __syncthreads();
+    float tbx, tby, tbz;
+    mr_target_mean(L, M, tbx, tby, tbz);
+    const int p = blockIdx.x * MP_THREADS + threadIdx.x;
+    if (p < P) {
+        const MrRec r = mr_record(L, starts + (size_t)p * S, S, M, tbx, tby, tbz);
+        float4* o = work + 2 * ((size_t)b * P + p);
+        o[0] = r.fit;
+        o[1] = r.quat;
+    }
+}
+
+template <bool SPILL>
+__global__ __launch_bounds__(MP_THREADS) void k_motif_rigid(const float* __restrict__ x0, int N, int P, int S, int M,
+                                                            const int32_t* __restrict__ seg_len, const int32_t* __restrict__ starts,
+                                                            const float* __restrict__ target, const float* __restrict__ var_p,
+                                                            const float4* __restrict__ work, float* __restrict__ logp,
+                                                            float* __restrict__ grad, int32_t* __restrict__ best,
+                                                            float* __restrict__ rmsd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mp_smem[];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const MpLds L = mp_carve(mp_smem, N, M, S, SPILL ? 0 : 2 * P);
+    mp_stage(L, x0 + (size_t)b * 3 * N, target, seg_len, N, M, S);
+    const float var = *var_p, two_var = 2.f * var;
+    __syncthreads();
+    float tbx, tby, tbz;
+    mr_target_mean(L, M, tbx, tby, tbz);
+    if (!SPILL)
+        for (int p = tid; p < P; p += MP_THREADS) {
+            const MrRec r = mr_record(L, starts + (size_t)p * S, S, M, tbx, tby, tbz);
+            L.rec[2 * p] = r.fit;
+            L.rec[2 * p + 1] = r.quat;
+        }
+    const float4* rec = SPILL ? work + 2 * (size_t)b * P : L.rec;
+    __syncthreads();
+
+    // score = -q / (2 var), in this one form wherever it is needed; logsumexp with the max taken first
+    float mx = -INFINITY;
+    for (int p = tid; p < P; p += MP_THREADS) mx = fmaxf(mx, -rec[2 * p].x / two_var);
+    mx = mp_block_max(mx, L.red);
+    float se = 0.f;
+    for (int p = tid; p < P; p += MP_THREADS) se += expf(-rec[2 * p].x / two_var - mx);
+    se = mp_block_sum(se, L.red);
+    if (logp && blockIdx.x == 0 && tid == 0) logp[b] = mx + logf(se) - logf((float)P);
+
+    // the lowest placement that reaches the max, and its RMSD
+    if (best || rmsd) {
+        int bp = P;
+        for (int p = tid; p < P; p += MP_THREADS)
+            if (p < bp && -rec[2 * p].x / two_var == mx) bp = p;
+        bp = mr_block_min(bp, L.wcnt);
+        if (bp >= P) bp = 0;                                  // (only a non-finite input gets here)
+        if (blockIdx.x == 0 && tid == 0) {
+            if (best) best[b] = bp;
+            if (rmsd) rmsd[b] = sqrtf(rec[2 * bp].x / (float)M);
+        }
+        __syncthreads();                                      // (wcnt is used again below)
+    }
+    if (!grad) return;
+
+    // the placements whose weight is not exactly 0, in ascending order: as k_motif_potential lists them
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int cap = mp_act_cap(P);
+    int cnt = 0;
+    for (int c0 = 0; c0 < P; c0 += MP_THREADS) {
+        const int p = c0 + tid;
+        const bool on = p < P && expf(-rec[2 * p].x / two_var - mx) != 0.f;
+        const uint64_t bal = __ballot(on);
+        if (lane == 0) L.wcnt[w] = __popcll(bal);
+        __syncthreads();
+        int at = cnt + __popcll(bal & ((1ull << lane) - 1));
+        for (int v = 0; v < MP_WAVES; ++v) {
+            if (v < w) at += L.wcnt[v];
+            cnt += L.wcnt[v];
+        }
+        if (on && at < cap) L.act[at] = p;
+        __syncthreads();
+    }
+    const bool listed = cnt <= cap;
+    const int K = listed ? cnt : P;
+
+    // gather: lane = residue, wave = a contiguous quarter of the (listed) placements; R from the record's quaternion (wave-uniform)
+    const int n = blockIdx.x * MP_TILE + lane;
+    const bool live = n < N;
+    const float xn = live ? L.xs[3 * n] : 0.f, yn = live ? L.xs[3 * n + 1] : 0.f, zn = live ? L.xs[3 * n + 2] : 0.f;
+    const int k0 = (int)((int64_t)K * w / MP_WAVES), k1 = (int)((int64_t)K * (w + 1) / MP_WAVES);
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int c0 = k0; c0 < k1; c0 += MP_CHUNK) {
+        const int c1 = min(c0 + MP_CHUNK, k1);
+        float bx = 0.f, by = 0.f, bz = 0.f;
+        for (int k = c0; k < c1; ++k) {
+            const int p = __builtin_amdgcn_readfirstlane(listed ? L.act[k] : k);
+            const float4 rp = rec[2 * p];
+            const float e = expf(-rp.x / two_var - mx);       // bitwise the term of `se`
+            if (e == 0.f) continue;                           // (wave-uniform)
+            const int32_t* st = starts + (size_t)p * S;
+            int m = -1;
+            for (int s = 0; s < S; ++s) {
+                const int d = n - st[s];
+                if ((unsigned)d < (unsigned)L.sl[s]) m = L.so[s] + d;
+            }
+            if (m >= 0) {
+                const MrRot R = mr_rotation(rec[2 * p + 1]);
+                const float* t = L.tg + 3 * m;
+                const float tx = t[0] - tbx, ty = t[1] - tby, tz = t[2] - tbz;
+                bx += e * ((xn - rp.y) - (R.xx * tx + R.xy * ty + R.xz * tz));
+                by += e * ((yn - rp.z) - (R.yx * tx + R.yy * ty + R.yz * tz));
+                bz += e * ((zn - rp.w) - (R.zx * tx + R.zy * ty + R.zz * tz));
+            }
+        }
+        ax += bx;
+        ay += by;
+        az += bz;
+    }
+    float* mine = L.part + 3 * (w * 64 + lane);
+    mine[0] = ax;
+    mine[1] = ay;
+    mine[2] = az;
+    __syncthreads();
+    if (w == 0 && live) {
+        float gx = L.part[3 * lane], gy = L.part[3 * lane + 1], gz = L.part[3 * lane + 2];
+        for (int v = 1; v < MP_WAVES; ++v) {
+            const float* o = L.part + 3 * (v * 64 + lane);
+            gx += o[0];
+            gy += o[1];
+            gz += o[2];
+        }
+        const float sc = -1.f / (var * se);
+        float* g = grad + ((size_t)b * N + n) * 3;
+        g[0] = gx * sc;
+        g[1] = gy * sc;
+        g[2] = gz * sc;
+    }
+}
+
 }  // namespace
 
 size_t genie_motif_potential_work_bytes(int B, int P) {
@@ -285,6 +600,45 @@ int genie_motif_potential(genie_stream_t stream, int B, int N, const float* x0, 
                                       (int)lds);
         hipLaunchKernelGGL(k_motif_potential<false>, grid, dim3(MP_THREADS), lds, st, x0, N, P, S, M, seg_len, starts, target, var,
                            (const float4*)nullptr, logp_out, grad_out);
+    }
+    return hipGetLastError() == hipSuccess ? GENIE_OK : GENIE_E_HIP;
+}
+
+size_t genie_motif_potential_rigid_work_bytes(int B, int P) {
+    return (B >= 1 && P > MR_LDS_P) ? (size_t)B * (size_t)P * 2 * sizeof(float4) : 0;
+}
+
+int genie_motif_potential_rigid(genie_stream_t stream, int B, int N, const float* x0, int P, int S, int M, const int32_t* seg_len,
+                                const int32_t* starts, const float* target, const float* var, float* logp_out, float* grad_out,
+                                int32_t* best_out, float* rmsd_out, void* work, size_t work_bytes) {
+    if (!x0 || !seg_len || !starts || !target || !var) return GENIE_E_ARG;
+    if ((logp_out == nullptr) != (grad_out == nullptr) || (!logp_out && !best_out && !rmsd_out)) return GENIE_E_ARG;
+    if (B < 1 || B > 65535 || N < 1 || P < 1 || S < 1 || M < 3 || M > N || S > M || (int64_t)P * S > INT32_MAX) return GENIE_E_ARG;
+    const bool spill = P > MR_LDS_P;
+    const size_t need = genie_motif_potential_rigid_work_bytes(B, P);
+    if (spill && (!work || work_bytes < need || (reinterpret_cast<uintptr_t>(work) & 15))) return GENIE_E_ARG;
+    const size_t lds = mp_lds_bytes(N, M, S, P, spill ? 0 : 2 * P);
+    if (lds > MP_LDS_MAX) return GENIE_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(grad_out ? (N + MP_TILE - 1) / MP_TILE : 1, B);          // without a gradient there is nothing to tile
+    if (spill) {
+        if (lds > 64 * 1024) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_motif_rigid_records), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_motif_rigid<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds);
+        }
+        float4* rec = static_cast<float4*>(work);
+        hipLaunchKernelGGL(k_motif_rigid_records, dim3((P + MP_THREADS - 1) / MP_THREADS, B), dim3(MP_THREADS), lds, st, x0, N, P, S, M,
+                           seg_len, starts, target, rec);
+        hipLaunchKernelGGL(k_motif_rigid<true>, grid, dim3(MP_THREADS), lds, st, x0, N, P, S, M, seg_len, starts, target, var,
+                           (const float4*)rec, logp_out, grad_out, best_out, rmsd_out);
+    } else {
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_motif_rigid<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds);
+        hipLaunchKernelGGL(k_motif_rigid<false>, grid, dim3(MP_THREADS), lds, st, x0, N, P, S, M, seg_len, starts, target, var,
+                           (const float4*)nullptr, logp_out, grad_out, best_out, rmsd_out);
     }
     return hipGetLastError() == hipSuccess ? GENIE_OK : GENIE_E_HIP;
 }

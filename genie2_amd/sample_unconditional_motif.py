@@ -5,7 +5,12 @@ flags and the unconditional CLI's output layout, outdir/pdbs/{length}_{index}.pd
 The reference hard-codes its motif (sampler/smc_sampler_new.py:155-157); here it is an explicit `--motif_file` in the REMARK 999
 format of the scaffold CLI.  Its motif entries, in file order, are the segments; their C-alpha coordinates come from the file's
 ATOM records.  Each batch is one particle system of `batch_size` particles guided by the fused motif potential (MotifPotential,
-csrc/smc_kernels.hip) over every placement of the segments in a structure of that length."""
+csrc/smc_kernels.hip) over every placement of the segments in a structure of that length.
+
+`--align rigid` guides with the superposed form of the potential, which does not depend on the orientation the motif file is written
+in.  `--write_motif_locations` adds outdir/motif_locations/{length}_{index}.txt beside each PDB: one `start\tend` line per segment
+(0-based, end inclusive: the format of the reference's motif_location.txt, unconditional_smc.py:334-343) for the placement that fits
+the sample best after optimal superposition, then a last line `# rmsd <motif RMSD of that fit in Angstrom>`."""
 import argparse
 import os
 
@@ -37,6 +42,17 @@ def load_motif_segments(filepath):
     return segments
 
 
+def write_motif_locations(fit, directory, length, offset):
+    """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: the segments' `start\tend`
+    lines of TwistedSampler.last_fit, then `# rmsd`."""
+    os.makedirs(directory, exist_ok=True)
+    for i, (starts, ends, rmsd) in enumerate(zip(fit['starts'].tolist(), fit['ends'].tolist(), fit['rmsd'].tolist())):
+        with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
+            for st, end in zip(starts, ends):
+                fh.write('{}\t{}\n'.format(st, end))
+            fh.write('# rmsd {:.3f}\n'.format(rmsd))
+
+
 class MotifRunner(UnconditionalRunner):
     def create_tasks(self, params):
         total = sum(len(s) for s in load_motif_segments(params['motif_file']))
@@ -49,6 +65,8 @@ class MotifRunner(UnconditionalRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
         c.update({k: params[k] for k in ('tausq', 'guidance_alpha', 'ess_threshold', 'last_unguided_steps', 'max_offsets')})
+        c['align'] = params.get('align', 'translation')
+        c['write_motif_locations'] = bool(params.get('write_motif_locations', False))
         c['segments'] = load_motif_segments(params['motif_file'])
         return c
 
@@ -70,12 +88,14 @@ class MotifRunner(UnconditionalRunner):
                     continue
                 # one particle system per batch; its placements drawn from numpy's global generator, as the reference does
                 potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
-                                           max_offsets=constants['max_offsets'], device=device)
+                                           max_offsets=constants['max_offsets'], device=device, align=constants['align'])
                 sampler.sample({
                     'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
                     'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps']})
+                if constants['write_motif_locations']:
+                    write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
                 remaining -= batch
 
 
@@ -105,6 +125,11 @@ def build_parser():
     p.add_argument('--max_offsets', type=int, default=1000,
                    help='Placements of the motif kept (a random subset when there are more) (not in the reference CLI)')
     p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist (not in the reference CLI)')
+    p.add_argument('--align', type=str, choices=('translation', 'rigid'), default='translation',
+                   help='Compare placements to the motif as the file orients it (translation) or after optimal superposition (rigid)')
+    p.add_argument('--write_motif_locations', action='store_true',
+                   help='Write outdir/motif_locations/{length}_{index}.txt: start and end residue of every motif segment in the '
+                        'best-fitting placement (0-based, inclusive) and the superposed motif RMSD')
     return p
 
 

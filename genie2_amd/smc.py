@@ -120,6 +120,8 @@ class TwistedSampler(UnconditionalSampler):
     potential is motif_twisting_function over all of them, unconditional_smc.py:303-345); optional 'tausq' with it;
     optional 'noise' [T,B,N,3] (initial draw + one per step, as BaseSampler), 'resample_u' (list of uniforms, tests),
     'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50).
+    After _sample, `last_fit` holds what the twisting function's `locate` says of the final coordinates (MotifPotential.locate: 'best',
+    'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample), or None when it has no `locate`.
     A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it."""
 
     def __init__(self, model):
@@ -192,6 +194,10 @@ class TwistedSampler(UnconditionalSampler):
                 log_w_acc = normalize_log_weights(log_w_acc, dim=0) + torch.log(torch.tensor(float(B), device=self.device))
             trans = new
             rots = eng.frenet(trans)
+        # where the motif ended up (MotifPotential.locate: the best placement of every sample and its superposed RMSD)
+        self.last_fit = None
+        if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
+            self.last_fit = {k: v.cpu() for k, v in twist.locate(trans.detach()).items()}
         feats['atom_positions'] = trans.detach().cpu()
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 
@@ -236,10 +242,18 @@ class MotifPotential:
     exactly as generate_motif_index_mask does, the concatenated target is centred as TwistedSampler centres it, and both are uploaded
     once.  The forward launches genie_motif_potential on torch's current stream and keeps the gradient it computes; the backward
     scales it.  Nothing on the per-step path reads device memory from the host: var = xstart_variance(alphas_cumprod[step], tausq)
-    stays on the device."""
+    stays on the device.
 
-    def __init__(self, segments, n_res, alphas_cumprod, tausq=0.012, max_offsets=1000, rng=None, device='cuda'):
+    `align='rigid'` guides with the superposed form instead (genie_motif_potential_rigid): every placement is compared to the motif
+    in its best-fitting orientation (a proper rotation), so the orientation the motif file is written in no longer matters.  It needs
+    at least 3 motif residues that are not collinear.  `locate(x)` reports, for either `align`, the best placement of every sample
+    and its motif RMSD after optimal superposition."""
+
+    def __init__(self, segments, n_res, alphas_cumprod, tausq=0.012, max_offsets=1000, rng=None, device='cuda', align='translation'):
         from . import capi
+        if align not in ('translation', 'rigid'):
+            raise ValueError("align must be 'translation' or 'rigid', got %r" % (align,))
+        self.align = align
         self.lib = capi.load_library()
         self.device = torch.device(device)
         if self.device.type != 'cuda':
@@ -250,6 +264,13 @@ class MotifPotential:
         self.seg_len = [len(x) for x in segs]
         if not segs or min(self.seg_len) < 1:
             raise ValueError('the motif needs at least one segment of at least one residue')
+        if align == 'rigid':                                             # (on the host, once, before any placement is drawn)
+            tgt = torch.cat(segs).double()
+            if len(tgt) < 3:
+                raise ValueError('a superposed fit needs at least 3 motif residues, got %d' % len(tgt))
+            sv = torch.linalg.svdvals(tgt - tgt.mean(dim=0, keepdim=True))
+            if float(sv[1]) < 1e-3 * float(sv[0]):
+                raise ValueError('the motif residues are collinear: their superposition has no unique rotation')
         self.n_res, self.tausq = int(n_res), float(tausq)
         self.locs = get_all_motif_locations(self.n_res, self.seg_len, max_offsets, rng)
         if not self.locs:
@@ -263,6 +284,8 @@ class MotifPotential:
         self.target = (tgt - tgt.mean(dim=0, keepdim=True)).contiguous()      # (as TwistedSampler, smc.py:133-140)
         self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
         self._work = torch.zeros(0, dtype=torch.uint8, device=self.device)
+        self.has_fit = self.M >= 3                                      # locate() superposes: three residues at least
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
 
     def variance(self, step):
         return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
@@ -270,13 +293,29 @@ class MotifPotential:
     def __call__(self, x0, step):
         return _MotifPotentialFn.apply(x0, self, self.variance(step))
 
-    def _launch(self, x0, var):
-        import ctypes as C
+    def locate(self, x):
+        """Where the motif is in x [B,N,3]: {'best' [B]: the placement that fits best after optimal superposition (the lowest
+        index of equal ones), 'rmsd' [B]: its motif RMSD, 'starts', 'ends' [B,S]: the residues its segments occupy, 0-based, end
+        inclusive (what the reference writes to motif_location.txt, unconditional_smc.py:334-343)}.  Always the superposed fit,
+        whatever `align` guides with; tensors on the potential's device."""
+        if not self.has_fit:
+            raise ValueError('a superposed fit needs at least 3 motif residues, got %d' % self.M)
+        best, rmsd = self._launch_rigid(self._checked(x), self._one, fit=True)     # (argmax of -q/2: var plays no part)
+        starts = self.starts[best.long()].long()
+        return {'best': best.long(), 'rmsd': rmsd, 'starts': starts, 'ends': starts + self.seg_len_t.long()[None] - 1}
+
+    def _checked(self, x0):
         if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
             raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
         if x0.device != self.device:
             raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
-        x = x0.detach().to(torch.float32).contiguous()
+        return x0.detach().to(torch.float32).contiguous()
+
+    def _launch(self, x0, var):
+        import ctypes as C
+        x = self._checked(x0)
+        if self.align == 'rigid':
+            return self._launch_rigid(x, var, fit=False)
         B = x.shape[0]
         need = self.lib.genie_motif_potential_work_bytes(B, self.P)
         if need > self._work.numel():
@@ -292,3 +331,27 @@ class MotifPotential:
             from . import capi
             raise capi.GenieError('genie_motif_potential failed (%d)' % rc)
         return logp, grad
+
+    def _launch_rigid(self, x, var, fit):
+        """genie_motif_potential_rigid on x (f32, contiguous): (best, rmsd) when `fit`, else (logp, grad)."""
+        import ctypes as C
+        B = x.shape[0]
+        need = self.lib.genie_motif_potential_rigid_work_bytes(B, self.P)
+        if need > self._work.numel():
+            self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
+        null = C.c_void_p(0)
+        p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
+        if fit:
+            a, b = torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, dtype=torch.float32, device=x.device)
+            outs = (null, null, p(a), p(b))
+        else:
+            a, b = torch.empty(B, dtype=torch.float32, device=x.device), torch.empty_like(x)
+            outs = (p(a), p(b), null, null)
+        with torch.cuda.device(x.device):
+            rc = self.lib.genie_motif_potential_rigid(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
+                                                      self.P, self.S, self.M, p(self.seg_len_t), p(self.starts), p(self.target), p(var),
+                                                      *outs, p(self._work) if need else null, self._work.numel())
+        if rc != 0:
+            from . import capi
+            raise capi.GenieError('genie_motif_potential_rigid failed (%d)' % rc)
+        return a, b

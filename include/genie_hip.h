@@ -159,6 +159,24 @@ int genie_motif_potential(genie_stream_t stream, int B, int N, const float* x0 /
                           size_t work_bytes);
 size_t genie_motif_potential_work_bytes(int B, int P);
 
+/* The same potential after optimal superposition: every placement is compared to the motif in its best-fitting orientation, not in
+ * the one the motif file happens to be written in.  With t_c = target - mean(target) and c_bp as above:
+ *   R_bp = argmin over proper rotations (det +1) of sum_m |c_bp(m) - R t_c(m)|^2     (Horn's quaternion, float32 Jacobi sweeps)
+ *   e_bp(m) = c_bp(m) - R_bp t_c(m),   q_bp = sum_m |e_bp(m)|^2   (summed from the residuals, not from the eigenvalue)
+ *   score[b,p] = -q_bp / (2 var),      logp_out[b] = logsumexp_p score[b,p] - log P
+ *   grad_out[b,n] = -sum_p w_bp [n in p] e_bp(m_p(n)) / var,  w_bp = softmax_p score[b,:]
+ * (the derivative through R vanishes at the optimum and sum_m e = 0; exactly 0 at residues no placement covers).
+ *   best_out[b] = the lowest p with the largest score,   rmsd_out[b] = sqrt(q_{b,best} / M): the superposed motif RMSD.
+ * A mirror image does not fit (R is proper); a collinear selection has no unique R but a unique score, and every output stays finite.
+ * logp_out and grad_out are given together or both NULL; best_out and rmsd_out may each be NULL; at least one output is asked for.
+ * Arguments, `work` (genie_motif_potential_rigid_work_bytes(B, P) bytes, 16-byte aligned; 0 = none needed), launches (one, or two when
+ * the placement records spill), reproducibility and the return value are as for genie_motif_potential; M < 3 is refused too. */
+int genie_motif_potential_rigid(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int P, int S, int M,
+                                const int32_t* seg_len /*[S]*/, const int32_t* starts /*[P,S]*/, const float* target /*[M,3]*/,
+                                const float* var /*[1], device*/, float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                                int32_t* best_out /*[B] or NULL*/, float* rmsd_out /*[B] or NULL*/, void* work, size_t work_bytes);
+size_t genie_motif_potential_rigid_work_bytes(int B, int P);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output

@@ -2,6 +2,8 @@
 motif (tests/golden/motif_problem_6E6R.pdb, segments of 6 and 7 residues) thinned to P = 1000 placements, at a mid-trajectory step.
 
     python tools/smc_step_time.py [--reps 50] [--warmup 5] [--step 500]     one JSON line of ms per call (device events)
+    python tools/smc_step_time.py --align rigid   the same line for the superposed potential (MotifPotential(align='rigid')) beside
+                                                  the fused translation one, without the PyTorch potential
     python tools/smc_step_time.py --trace K       K twisted steps with each potential, each run between two torch.cuda._sleep
                                                   marker kernels (for rocprofv3 --kernel-trace --stats)
     python tools/smc_step_time.py --digest DIR    launches and kernel time per step from the kernel_trace.csv under DIR
@@ -50,7 +52,9 @@ def setup(B=8, N=256, P=1000, step=500, dev='cuda:0'):
     np.random.seed(0)                                        # the same placements
     pot = MotifPotential(segs, N, abar, max_offsets=P, device=dev)
     assert pot.P == pm.shape[0] == P
-    potentials = {'torch': lambda x, s: motif_twisting_function(x, pm, tgt, abar[s], 0.012), 'fused': pot}
+    np.random.seed(0)
+    rigid = MotifPotential(segs, N, abar, max_offsets=P, device=dev, align='rigid')
+    potentials = {'torch': lambda x, s: motif_twisting_function(x, pm, tgt, abar[s], 0.012), 'fused': pot, 'rigid': rigid}
     return dict(eng=eng, w=w, sched=sched, trans=trans, rots=eng.frenet(trans), step=step, B=B, N=N, P=P, potentials=potentials,
                 noise=torch.randn(B, N, 3, generator=g).to(dev), mask=torch.ones(B, N, 1, device=dev))
 
@@ -117,6 +121,15 @@ def timing(args):
            'motif': '6E6R (6 + 7 residues)', 'device': torch.cuda.get_device_name(0)}
     res['denoise_ms'] = time_ms(lambda: eng.denoise(ctx['trans'], ctx['rots'], ts), args.reps, args.warmup)
     res['denoise_vjp_ms'] = time_ms(lambda: eng.denoise_vjp(ctx['w'], ctx['trans'], ctx['rots'], ts, dz), args.reps, args.warmup)
+    if args.align == 'rigid':
+        res['align'] = 'rigid'
+        for k in ('fused', 'rigid'):
+            res[k + '_potential_ms'] = time_ms(lambda: potential_call(ctx, pt[k]), args.reps, args.warmup)
+        res['rigid_locate_ms'] = time_ms(lambda: pt['rigid'].locate(ctx['trans']), args.reps, args.warmup)
+        for k in ('fused', 'rigid'):
+            res[k + '_step_ms'] = time_ms(lambda: twisted_step(ctx, pt[k]), args.reps, args.warmup)
+        print(json.dumps(res))
+        return
     for k in ('torch', 'fused'):
         res[k + '_potential_ms'] = time_ms(lambda: potential_call(ctx, pt[k]), args.reps, args.warmup)
     for k in ('torch', 'fused'):
@@ -181,6 +194,7 @@ def main():
     ap.add_argument('--reps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--step', type=int, default=500)
+    ap.add_argument('--align', choices=('translation', 'rigid'), default='translation')
     ap.add_argument('--trace', type=int, default=0)
     ap.add_argument('--digest', type=str, default=None)
     ap.add_argument('--steps', type=int, default=3, help='(--digest) steps per window of the traced run')
