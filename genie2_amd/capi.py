@@ -98,7 +98,13 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_size_t]),
     'genie_motif_potential_rigid_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'genie_motif_potential_grouped': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    'genie_motif_potential_grouped_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
 }
+
+MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
 
 _lib = None
 

@@ -17,7 +17,8 @@
 // of the listed placements in order and the four partial sums are added in wave order.  No atomics, no scatter: every output is written once, in a fixed order, so results are
 // bitwise reproducible.  Up to MP_LDS_P placements the records live in LDS (one launch); beyond that a first kernel writes them to the
 // caller's `work` and the main kernel reads them from there (two launches).  `starts` is trusted (the caller validates it once when it
-// builds it); it only ever indexes LDS.
+// builds it); it only ever indexes LDS.  Two more forms follow, each with its own section below: the superposed one
+// (genie_motif_potential_rigid) and the group-wise one for multi-motif problems (genie_motif_potential_grouped).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -565,6 +566,360 @@ __global__ __launch_bounds__(MP_THREADS) void k_motif_rigid(const float* __restr
     }
 }
 
+// ---- the group-wise form: genie_motif_potential_grouped ---------------------------------------------------------------------------
+// A multi-motif problem: segment s belongs to group seg_group[s] (0..G-1); the segments of one group keep their relative pose, the
+// groups move independently, so every group is superposed (or, align 0, translated) on its own.  For group g with M_g residues:
+//   c^g_bp(m) = x0[b, r_p(m)] - mean_{m in g} x0[b, r_p(m)],   t^g(m) = target[m] - mean_{m in g} target[m]
+//   e^g_bp(m) = c^g_bp(m) - R^g_bp t^g(m)   (R^g = I, or the proper rotation that minimises sum_{m in g} |e^g|^2: mr_quaternion)
+//   q_bp = sum_g q^g_bp,  q^g_bp = sum_{m in g} |e^g_bp(m)|^2   (summed from the residuals, the groups added in group order)
+//   score[b,p] = -q_bp / (2 var),   logp, w, best as above,   grad[b,n] = -sum_p w_bp [n in p] e^{g(n)}_bp(m_p(n)) / var
+//   rmsd[b] = sqrt(q_{b,best} / M),   group_rmsd[b,g] = sqrt(q^g_{b,best} / M_g)
+// (sum_{m in g} e^g = 0 because both sides are centred per group, so the translation form needs no mean term either.)  Placements stay
+// joint: one softmax over p, the segments of all groups in file order.
+//
+// Layout as above.  The record of a placement is per group: (q^g, centroid of g) and, for the rigid fit, g's quaternion, G * rw float4
+// (rw = 1 or 2), followed for all placements by the totals q_p, one float each.  They stay in LDS while they fit in MG_LDS_REC bytes
+// and spill to `work` beyond.  The target is centred per group once, in LDS, when it is staged.  In the gather a lane's residue picks
+// the group, so the record (and R) is read per lane; the weight stays wave-uniform.
+constexpr size_t MG_LDS_REC = 96 * 1024;         // bytes of placement records kept in LDS; more spill to `work`
+
+// float4 slots of one particle's records: P * G * rw of them, then the P totals padded to whole slots
+__host__ __device__ inline size_t mg_slots(int P, int G, int rw) { return (size_t)P * G * rw + ((size_t)P + 3) / 4; }
+
+// dynamic LDS: [rec: float4 x P_lds*G*rw] [qt: P_lds floats, padded] [xs: 3N] [tg: 3M] [gm: 3G] [part: WAVES*64*3] [red: 2*WAVES]
+//              [sl, so, sg: 3S int] [gn: G int] [wcnt: WAVES int] [act: mp_act_cap(P) int]
+size_t mg_lds_bytes(int N, int M, int S, int G, int P, int P_lds, int rw) {
+    return mg_slots(P_lds, G, rw) * sizeof(float4) +
+           sizeof(float) * (3 * (size_t)N + 3 * (size_t)M + 3 * (size_t)G + MP_WAVES * 64 * 3 + 2 * MP_WAVES) +
+           sizeof(int) * (3 * (size_t)S + G + MP_WAVES + mp_act_cap(P));
+}
+
+struct MgLds {
+    float4* rec;
+    float *qt, *xs, *tg, *gm, *part, *red;
+    int *sl, *so, *sg, *gn, *wcnt, *act;
+};
+
+__device__ inline MgLds mg_carve(unsigned char* base, int N, int M, int S, int G, int P_lds, int rw) {
+    MgLds L;
+    L.rec = reinterpret_cast<float4*>(base);
+    L.qt = reinterpret_cast<float*>(L.rec + (size_t)P_lds * G * rw);
+    L.xs = reinterpret_cast<float*>(L.rec + mg_slots(P_lds, G, rw));
+    L.tg = L.xs + 3 * N;
+    L.gm = L.tg + 3 * M;
+    L.part = L.gm + 3 * G;
+    L.red = L.part + MP_WAVES * 64 * 3;
+    L.sl = reinterpret_cast<int*>(L.red + 2 * MP_WAVES);
+    L.so = L.sl + S;
+    L.sg = L.so + S;
+    L.gn = L.sg + S;
+    L.wcnt = L.gn + G;
+    L.act = L.wcnt + MP_WAVES;
+    return L;
+}
+
+// x0[b], the target and the segment table into LDS; then every group's target mean and size (one thread per group, its residues in
+// motif order) and the target centred per group in place.  Ends with the block in step.  (seg_group is the caller's, validated where
+// it is built; it is clamped all the same: it indexes LDS.)
+__device__ inline void mg_stage(const MgLds& L, const float* __restrict__ x0b, const float* __restrict__ target,
+                                const int32_t* __restrict__ seg_len, const int32_t* __restrict__ seg_group, int N, int M, int S, int G) {
+    for (int i = threadIdx.x; i < 3 * N; i += MP_THREADS) L.xs[i] = x0b[i];
+    for (int i = threadIdx.x; i < 3 * M; i += MP_THREADS) L.tg[i] = target[i];
+    if (threadIdx.x == 0) {
+        int off = 0;
+        for (int s = 0; s < S; ++s) {
+            const int n = seg_len[s];
+            L.sl[s] = n;
+            L.so[s] = off;
+            L.sg[s] = min(max(seg_group[s], 0), G - 1);
+            off += n;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < G) {
+        const int g = threadIdx.x;
+        float tx = 0.f, ty = 0.f, tz = 0.f;
+        int cnt = 0;
+        for (int s = 0; s < S; ++s) {
+            if (L.sg[s] != g) continue;
+            const int n = L.sl[s], m0 = L.so[s];
+            for (int i = 0; i < n; ++i) {
+                const float* t = L.tg + 3 * (m0 + i);
+                tx += t[0];
+                ty += t[1];
+                tz += t[2];
+            }
+            cnt += n;
+        }
+        L.gm[3 * g] = tx / (float)cnt;
+        L.gm[3 * g + 1] = ty / (float)cnt;
+        L.gm[3 * g + 2] = tz / (float)cnt;
+        L.gn[g] = cnt;
+    }
+    __syncthreads();
+    for (int m = threadIdx.x; m < M; m += MP_THREADS) {
+        int g = 0;
+        for (int s = 0; s < S; ++s)
+            if ((unsigned)(m - L.so[s]) < (unsigned)L.sl[s]) g = L.sg[s];
+        L.tg[3 * m] -= L.gm[3 * g];
+        L.tg[3 * m + 1] -= L.gm[3 * g + 1];
+        L.tg[3 * m + 2] -= L.gm[3 * g + 2];
+    }
+    __syncthreads();
+}
+
+// the G records of one placement to out[0 .. G*rw) (LDS or `work`); returns q_p.  L.tg is centred per group.
+template <bool RIGID>
+__device__ __forceinline__ float mg_record(const MgLds& L, const int32_t* __restrict__ st, int S, int G, float4* out) {
+    float qp = 0.f;
+    for (int g = 0; g < G; ++g) {
+        const float ng = (float)L.gn[g];
+        float cx = 0.f, cy = 0.f, cz = 0.f;
+        for (int s = 0; s < S; ++s) {
+            if (L.sg[s] != g) continue;
+            const int r0 = st[s], n = L.sl[s];
+            for (int i = 0; i < n; ++i) {
+                const float* x = L.xs + 3 * (r0 + i);
+                cx += x[0];
+                cy += x[1];
+                cz += x[2];
+            }
+        }
+        cx /= ng;
+        cy /= ng;
+        cz /= ng;
+        float q = 0.f;
+        if (RIGID) {
+            float Sxx = 0.f, Sxy = 0.f, Sxz = 0.f, Syx = 0.f, Syy = 0.f, Syz = 0.f, Szx = 0.f, Szy = 0.f, Szz = 0.f;
+            for (int s = 0; s < S; ++s) {
+                if (L.sg[s] != g) continue;
+                const int r0 = st[s], n = L.sl[s], m0 = L.so[s];
+                for (int i = 0; i < n; ++i) {
+                    const float* x = L.xs + 3 * (r0 + i);
+                    const float* t = L.tg + 3 * (m0 + i);
+                    const float ux = x[0] - cx, uy = x[1] - cy, uz = x[2] - cz, tx = t[0], ty = t[1], tz = t[2];
+                    Sxx += tx * ux;
+                    Sxy += tx * uy;
+                    Sxz += tx * uz;
+                    Syx += ty * ux;
+                    Syy += ty * uy;
+                    Syz += ty * uz;
+                    Szx += tz * ux;
+                    Szy += tz * uy;
+                    Szz += tz * uz;
+                }
+            }
+            const float4 qt = mr_quaternion(Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz);
+            const MrRot R = mr_rotation(qt);
+            for (int s = 0; s < S; ++s) {
+                if (L.sg[s] != g) continue;
+                const int r0 = st[s], n = L.sl[s], m0 = L.so[s];
+                for (int i = 0; i < n; ++i) {
+                    const float* x = L.xs + 3 * (r0 + i);
+                    const float* t = L.tg + 3 * (m0 + i);
+                    const float tx = t[0], ty = t[1], tz = t[2];
+                    const float ex = (x[0] - cx) - (R.xx * tx + R.xy * ty + R.xz * tz);
+                    const float ey = (x[1] - cy) - (R.yx * tx + R.yy * ty + R.yz * tz);
+                    const float ez = (x[2] - cz) - (R.zx * tx + R.zy * ty + R.zz * tz);
+                    q += ex * ex + ey * ey + ez * ez;
+                }
+            }
+            out[2 * g + 1] = qt;
+        } else {
+            for (int s = 0; s < S; ++s) {
+                if (L.sg[s] != g) continue;
+                const int r0 = st[s], n = L.sl[s], m0 = L.so[s];
+                for (int i = 0; i < n; ++i) {
+                    const float* x = L.xs + 3 * (r0 + i);
+                    const float* t = L.tg + 3 * (m0 + i);
+                    const float ex = (x[0] - cx) - t[0], ey = (x[1] - cy) - t[1], ez = (x[2] - cz) - t[2];
+                    q += ex * ex + ey * ey + ez * ez;
+                }
+            }
+        }
+        out[(RIGID ? 2 : 1) * g] = make_float4(q, cx, cy, cz);
+        qp += q;
+    }
+    return qp;
+}
+
+// large-P path, first launch: one placement per thread, records and totals to work[b]
+template <bool RIGID>
+__global__ __launch_bounds__(MP_THREADS) void k_motif_grouped_records(const float* __restrict__ x0, int N, int P, int S, int M, int G,
+                                                                      const int32_t* __restrict__ seg_len,
+                                                                      const int32_t* __restrict__ seg_group,
+                                                                      const int32_t* __restrict__ starts, const float* __restrict__ target,
+                                                                      float4* __restrict__ work) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mp_smem[];
+    constexpr int RW = RIGID ? 2 : 1;
+    const int b = blockIdx.y;
+    const MgLds L = mg_carve(mp_smem, N, M, S, G, 0, RW);          // (act / wcnt unused here)
+    mg_stage(L, x0 + (size_t)b * 3 * N, target, seg_len, seg_group, N, M, S, G);
+    const int p = blockIdx.x * MP_THREADS + threadIdx.x;
+    if (p < P) {
+        float4* rec = work + (size_t)b * mg_slots(P, G, RW);
+        reinterpret_cast<float*>(rec + (size_t)P * G * RW)[p] = mg_record<RIGID>(L, starts + (size_t)p * S, S, G, rec + (size_t)p * G * RW);
+    }
+}
+
+template <bool SPILL, bool RIGID>
+__global__ __launch_bounds__(MP_THREADS) void k_motif_grouped(const float* __restrict__ x0, int N, int P, int S, int M, int G,
+                                                              const int32_t* __restrict__ seg_len, const int32_t* __restrict__ seg_group,
+                                                              const int32_t* __restrict__ starts, const float* __restrict__ target,
+                                                              const float* __restrict__ var_p, const float4* __restrict__ work,
+                                                              float* __restrict__ logp, float* __restrict__ grad,
+                                                              int32_t* __restrict__ best, float* __restrict__ rmsd,
+                                                              float* __restrict__ group_rmsd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mp_smem[];
+    constexpr int RW = RIGID ? 2 : 1;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const MgLds L = mg_carve(mp_smem, N, M, S, G, SPILL ? 0 : P, RW);
+    const float var = *var_p, two_var = 2.f * var;
+    mg_stage(L, x0 + (size_t)b * 3 * N, target, seg_len, seg_group, N, M, S, G);
+    if (!SPILL)
+        for (int p = tid; p < P; p += MP_THREADS) L.qt[p] = mg_record<RIGID>(L, starts + (size_t)p * S, S, G, L.rec + (size_t)p * G * RW);
+    const float4* rec = SPILL ? work + (size_t)b * mg_slots(P, G, RW) : L.rec;
+    const float* qt = SPILL ? reinterpret_cast<const float*>(rec + (size_t)P * G * RW) : L.qt;
+    __syncthreads();
+
+    // score = -q / (2 var), in this one form wherever it is needed; logsumexp with the max taken first
+    float mx = -INFINITY;
+    for (int p = tid; p < P; p += MP_THREADS) mx = fmaxf(mx, -qt[p] / two_var);
+    mx = mp_block_max(mx, L.red);
+    float se = 0.f;
+    for (int p = tid; p < P; p += MP_THREADS) se += expf(-qt[p] / two_var - mx);
+    se = mp_block_sum(se, L.red);
+    if (logp && blockIdx.x == 0 && tid == 0) logp[b] = mx + logf(se) - logf((float)P);
+
+    // the lowest placement that reaches the max, its RMSD and that of every group in it
+    if (best || rmsd || group_rmsd) {
+        int bp = P;
+        for (int p = tid; p < P; p += MP_THREADS)
+            if (p < bp && -qt[p] / two_var == mx) bp = p;
+        bp = mr_block_min(bp, L.wcnt);
+        if (bp >= P) bp = 0;                                  // (only a non-finite input gets here)
+        if (blockIdx.x == 0) {
+            if (tid == 0 && best) best[b] = bp;
+            if (tid == 0 && rmsd) rmsd[b] = sqrtf(qt[bp] / (float)M);
+            if (tid < G && group_rmsd) group_rmsd[(size_t)b * G + tid] = sqrtf(rec[((size_t)bp * G + tid) * RW].x / (float)L.gn[tid]);
+        }
+        __syncthreads();                                      // (wcnt is used again below)
+    }
+    if (!grad) return;
+
+    // the placements whose weight is not exactly 0, in ascending order: as k_motif_potential lists them
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int cap = mp_act_cap(P);
+    int cnt = 0;
+    for (int c0 = 0; c0 < P; c0 += MP_THREADS) {
+        const int p = c0 + tid;
+        const bool on = p < P && expf(-qt[p] / two_var - mx) != 0.f;
+        const uint64_t bal = __ballot(on);
+        if (lane == 0) L.wcnt[w] = __popcll(bal);
+        __syncthreads();
+        int at = cnt + __popcll(bal & ((1ull << lane) - 1));
+        for (int v = 0; v < MP_WAVES; ++v) {
+            if (v < w) at += L.wcnt[v];
+            cnt += L.wcnt[v];
+        }
+        if (on && at < cap) L.act[at] = p;
+        __syncthreads();
+    }
+    const bool listed = cnt <= cap;
+    const int K = listed ? cnt : P;
+
+    // gather: lane = residue, wave = a contiguous quarter of the (listed) placements; the residue's segment picks the group, and with
+    // it the centroid and R of the record (per lane; the weight is wave-uniform)
+    const int n = blockIdx.x * MP_TILE + lane;
+    const bool live = n < N;
+    const float xn = live ? L.xs[3 * n] : 0.f, yn = live ? L.xs[3 * n + 1] : 0.f, zn = live ? L.xs[3 * n + 2] : 0.f;
+    const int k0 = (int)((int64_t)K * w / MP_WAVES), k1 = (int)((int64_t)K * (w + 1) / MP_WAVES);
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int c0 = k0; c0 < k1; c0 += MP_CHUNK) {
+        const int c1 = min(c0 + MP_CHUNK, k1);
+        float bx = 0.f, by = 0.f, bz = 0.f;
+        for (int k = c0; k < c1; ++k) {
+            const int p = __builtin_amdgcn_readfirstlane(listed ? L.act[k] : k);
+            const float e = expf(-qt[p] / two_var - mx);      // bitwise the term of `se`
+            if (e == 0.f) continue;                           // (wave-uniform)
+            const int32_t* st = starts + (size_t)p * S;
+            int m = -1, g = 0;
+            for (int s = 0; s < S; ++s) {
+                const int d = n - st[s];
+                if ((unsigned)d < (unsigned)L.sl[s]) {
+                    m = L.so[s] + d;
+                    g = L.sg[s];
+                }
+            }
+            if (m >= 0) {
+                const float4* rg = rec + ((size_t)p * G + g) * RW;
+                const float4 rp = rg[0];
+                const float* t = L.tg + 3 * m;
+                if (RIGID) {
+                    const MrRot R = mr_rotation(rg[1]);
+                    const float tx = t[0], ty = t[1], tz = t[2];
+                    bx += e * ((xn - rp.y) - (R.xx * tx + R.xy * ty + R.xz * tz));
+                    by += e * ((yn - rp.z) - (R.yx * tx + R.yy * ty + R.yz * tz));
+                    bz += e * ((zn - rp.w) - (R.zx * tx + R.zy * ty + R.zz * tz));
+                } else {
+                    bx += e * ((xn - rp.y) - t[0]);
+                    by += e * ((yn - rp.z) - t[1]);
+                    bz += e * ((zn - rp.w) - t[2]);
+                }
+            }
+        }
+        ax += bx;
+        ay += by;
+        az += bz;
+    }
+    float* mine = L.part + 3 * (w * 64 + lane);
+    mine[0] = ax;
+    mine[1] = ay;
+    mine[2] = az;
+    __syncthreads();
+    if (w == 0 && live) {
+        float gx = L.part[3 * lane], gy = L.part[3 * lane + 1], gz = L.part[3 * lane + 2];
+        for (int v = 1; v < MP_WAVES; ++v) {
+            const float* o = L.part + 3 * (v * 64 + lane);
+            gx += o[0];
+            gy += o[1];
+            gz += o[2];
+        }
+        const float sc = -1.f / (var * se);
+        float* gout = grad + ((size_t)b * N + n) * 3;
+        gout[0] = gx * sc;
+        gout[1] = gy * sc;
+        gout[2] = gz * sc;
+    }
+}
+
+template <bool RIGID>
+int mg_launch(hipStream_t st, int B, int N, const float* x0, int P, int S, int M, int G, const int32_t* seg_len, const int32_t* seg_group,
+              const int32_t* starts, const float* target, const float* var, float* logp, float* grad, int32_t* best, float* rmsd,
+              float* group_rmsd, void* work, bool spill, size_t lds) {
+    const dim3 grid(grad ? (N + MP_TILE - 1) / MP_TILE : 1, B);          // without a gradient there is nothing to tile
+    if (spill) {
+        if (lds > 64 * 1024) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_motif_grouped_records<RIGID>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_motif_grouped<true, RIGID>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }
+        float4* rec = static_cast<float4*>(work);
+        hipLaunchKernelGGL(k_motif_grouped_records<RIGID>, dim3((P + MP_THREADS - 1) / MP_THREADS, B), dim3(MP_THREADS), lds, st, x0, N, P,
+                           S, M, G, seg_len, seg_group, starts, target, rec);
+        hipLaunchKernelGGL((k_motif_grouped<true, RIGID>), grid, dim3(MP_THREADS), lds, st, x0, N, P, S, M, G, seg_len, seg_group, starts,
+                           target, var, (const float4*)rec, logp, grad, best, rmsd, group_rmsd);
+    } else {
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_motif_grouped<false, RIGID>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((k_motif_grouped<false, RIGID>), grid, dim3(MP_THREADS), lds, st, x0, N, P, S, M, G, seg_len, seg_group, starts,
+                           target, var, (const float4*)nullptr, logp, grad, best, rmsd, group_rmsd);
+    }
+    return hipGetLastError() == hipSuccess ? GENIE_OK : GENIE_E_HIP;
+}
+
 }  // namespace
 
 size_t genie_motif_potential_work_bytes(int B, int P) {
@@ -641,4 +996,32 @@ int genie_motif_potential_rigid(genie_stream_t stream, int B, int N, const float
                            (const float4*)nullptr, logp_out, grad_out, best_out, rmsd_out);
     }
     return hipGetLastError() == hipSuccess ? GENIE_OK : GENIE_E_HIP;
+}
+
+size_t genie_motif_potential_grouped_work_bytes(int B, int P, int G, int align) {
+    if (B < 1 || P < 1 || G < 1 || G > GENIE_MOTIF_MAX_GROUPS || (align != 0 && align != 1)) return 0;
+    const size_t bytes = mg_slots(P, G, align ? 2 : 1) * sizeof(float4);
+    return bytes > MG_LDS_REC ? (size_t)B * bytes : 0;
+}
+
+int genie_motif_potential_grouped(genie_stream_t stream, int B, int N, const float* x0, int P, int S, int M, int G, const int32_t* seg_len,
+                                  const int32_t* seg_group, const int32_t* starts, const float* target, const float* var, int align,
+                                  float* logp_out, float* grad_out, int32_t* best_out, float* rmsd_out, float* group_rmsd_out, void* work,
+                                  size_t work_bytes) {
+    if (!x0 || !seg_len || !seg_group || !starts || !target || !var) return GENIE_E_ARG;
+    if ((logp_out == nullptr) != (grad_out == nullptr) || (!logp_out && !best_out && !rmsd_out && !group_rmsd_out)) return GENIE_E_ARG;
+    if (B < 1 || B > 65535 || N < 1 || P < 1 || S < 1 || M < 1 || M > N || S > M || (int64_t)P * S > INT32_MAX) return GENIE_E_ARG;
+    if (G < 1 || G > GENIE_MOTIF_MAX_GROUPS || G > S || (align != 0 && align != 1)) return GENIE_E_ARG;
+    if (align == 1 && M < 3 * G) return GENIE_E_ARG;          // (every group needs 3 residues: the caller checks seg_len itself)
+    const int rw = align ? 2 : 1;
+    const size_t need = genie_motif_potential_grouped_work_bytes(B, P, G, align);
+    const bool spill = need > 0;
+    if (spill && (!work || work_bytes < need || (reinterpret_cast<uintptr_t>(work) & 15))) return GENIE_E_ARG;
+    const size_t lds = mg_lds_bytes(N, M, S, G, P, spill ? 0 : P, rw);
+    if (lds > MP_LDS_MAX) return GENIE_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    return align ? mg_launch<true>(st, B, N, x0, P, S, M, G, seg_len, seg_group, starts, target, var, logp_out, grad_out, best_out, rmsd_out,
+                                   group_rmsd_out, work, spill, lds)
+                 : mg_launch<false>(st, B, N, x0, P, S, M, G, seg_len, seg_group, starts, target, var, logp_out, grad_out, best_out,
+                                    rmsd_out, group_rmsd_out, work, spill, lds);
 }

@@ -10,7 +10,12 @@ csrc/smc_kernels.hip) over every placement of the segments in a structure of tha
 `--align rigid` guides with the superposed form of the potential, which does not depend on the orientation the motif file is written
 in.  `--write_motif_locations` adds outdir/motif_locations/{length}_{index}.txt beside each PDB: one `start\tend` line per segment
 (0-based, end inclusive: the format of the reference's motif_location.txt, unconditional_smc.py:334-343) for the placement that fits
-the sample best after optimal superposition, then a last line `# rmsd <motif RMSD of that fit in Angstrom>`."""
+the sample best after optimal superposition, then a last line `# rmsd <motif RMSD of that fit in Angstrom>`.
+
+`--motif_groups file` reads the motif group of every segment from the problem file (column 29 of REMARK 999 INPUT, as the scaffold
+CLI does): segments of one group keep their relative pose, different groups are guided as independent bodies, and the location files
+end with one more line per group, `# rmsd group <label> <that group's own RMSD>`.  The default, `joint`, treats all segments as one
+rigid motif."""
 import argparse
 import os
 
@@ -42,15 +47,23 @@ def load_motif_segments(filepath):
     return segments
 
 
+def load_motif_groups(filepath):
+    """The motif group label of every segment load_motif_segments returns, in the same order (column 29 of REMARK 999 INPUT)."""
+    return [st['group'] for st in load_motif_spec(filepath)['structures'] if st['type'] == 'motif']
+
+
 def write_motif_locations(fit, directory, length, offset):
     """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: the segments' `start\tend`
-    lines of TwistedSampler.last_fit, then `# rmsd`."""
+    lines of TwistedSampler.last_fit, then `# rmsd`; with motif groups one `# rmsd group <label>` line per group after it."""
     os.makedirs(directory, exist_ok=True)
     for i, (starts, ends, rmsd) in enumerate(zip(fit['starts'].tolist(), fit['ends'].tolist(), fit['rmsd'].tolist())):
         with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
             for st, end in zip(starts, ends):
                 fh.write('{}\t{}\n'.format(st, end))
             fh.write('# rmsd {:.3f}\n'.format(rmsd))
+            if 'group_rmsd' in fit:
+                for label, value in zip(fit['groups'], fit['group_rmsd'][i].tolist()):
+                    fh.write('# rmsd group {} {:.3f}\n'.format(label, value))
 
 
 class MotifRunner(UnconditionalRunner):
@@ -68,6 +81,8 @@ class MotifRunner(UnconditionalRunner):
         c['align'] = params.get('align', 'translation')
         c['write_motif_locations'] = bool(params.get('write_motif_locations', False))
         c['segments'] = load_motif_segments(params['motif_file'])
+        c['motif_groups'] = params.get('motif_groups', 'joint')
+        c['groups'] = load_motif_groups(params['motif_file']) if c['motif_groups'] == 'file' else None
         return c
 
     def execute(self, constants, tasks, device):
@@ -88,7 +103,8 @@ class MotifRunner(UnconditionalRunner):
                     continue
                 # one particle system per batch; its placements drawn from numpy's global generator, as the reference does
                 potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
-                                           max_offsets=constants['max_offsets'], device=device, align=constants['align'])
+                                           max_offsets=constants['max_offsets'], device=device, align=constants['align'],
+                                           groups=constants.get('groups'))
                 sampler.sample({
                     'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
@@ -127,6 +143,9 @@ def build_parser():
     p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist (not in the reference CLI)')
     p.add_argument('--align', type=str, choices=('translation', 'rigid'), default='translation',
                    help='Compare placements to the motif as the file orients it (translation) or after optimal superposition (rigid)')
+    p.add_argument('--motif_groups', type=str, choices=('joint', 'file'), default='joint',
+                   help='Treat all motif segments as one rigid motif (joint) or guide every motif group of the problem file as a body '
+                        'of its own (file)')
     p.add_argument('--write_motif_locations', action='store_true',
                    help='Write outdir/motif_locations/{length}_{index}.txt: start and end residue of every motif segment in the '
                         'best-fitting placement (0-based, inclusive) and the superposed motif RMSD')

@@ -121,7 +121,8 @@ class TwistedSampler(UnconditionalSampler):
     optional 'noise' [T,B,N,3] (initial draw + one per step, as BaseSampler), 'resample_u' (list of uniforms, tests),
     'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50).
     After _sample, `last_fit` holds what the twisting function's `locate` says of the final coordinates (MotifPotential.locate: 'best',
-    'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample), or None when it has no `locate`.
+    'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample; with motif groups also 'group_rmsd' and the 'groups' labels),
+    or None when it has no `locate`.
     A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it."""
 
     def __init__(self, model):
@@ -197,7 +198,7 @@ class TwistedSampler(UnconditionalSampler):
         # where the motif ended up (MotifPotential.locate: the best placement of every sample and its superposed RMSD)
         self.last_fit = None
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
-            self.last_fit = {k: v.cpu() for k, v in twist.locate(trans.detach()).items()}
+            self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans.detach()).items()}
         feats['atom_positions'] = trans.detach().cpu()
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 
@@ -208,6 +209,29 @@ def placement_starts(locs):
     if not locs:
         return torch.zeros(0, 0, dtype=torch.int32)
     return torch.tensor([[st for st, _ in pl] for pl in locs], dtype=torch.int32)
+
+
+def canonical_groups(groups, n_segments):
+    """One hashable label per segment -> (labels in order of first appearance, group index of every segment): B, A, B gives
+    ([B, A], [0, 1, 0])."""
+    groups = list(groups)
+    if len(groups) != n_segments:
+        raise ValueError('groups needs one label per segment: %d labels for %d segments' % (len(groups), n_segments))
+    labels = []
+    for g in groups:
+        if g not in labels:
+            labels.append(g)
+    return labels, [labels.index(g) for g in groups]
+
+
+def _check_superposable(xyz, what):
+    """A superposed fit of these residues [n, 3] has a unique rotation: three at least, not on one line."""
+    xyz = xyz.double()
+    if len(xyz) < 3:
+        raise ValueError('a superposed fit needs at least 3 motif residues, got %d%s' % (len(xyz), what))
+    sv = torch.linalg.svdvals(xyz - xyz.mean(dim=0, keepdim=True))
+    if float(sv[1]) < 1e-3 * float(sv[0]):
+        raise ValueError('the motif residues%s are collinear: their superposition has no unique rotation' % what)
 
 
 def _check_starts(starts, seg_len, n_res):
@@ -247,30 +271,43 @@ class MotifPotential:
     `align='rigid'` guides with the superposed form instead (genie_motif_potential_rigid): every placement is compared to the motif
     in its best-fitting orientation (a proper rotation), so the orientation the motif file is written in no longer matters.  It needs
     at least 3 motif residues that are not collinear.  `locate(x)` reports, for either `align`, the best placement of every sample
-    and its motif RMSD after optimal superposition."""
+    and its motif RMSD after optimal superposition.
 
-    def __init__(self, segments, n_res, alphas_cumprod, tausq=0.012, max_offsets=1000, rng=None, device='cuda', align='translation'):
+    `groups` (one hashable label per segment, e.g. load_motif_groups of the problem file) makes it a multi-motif problem: the segments
+    of one group keep their relative pose, different groups are independent bodies.  With two or more distinct labels every group is
+    translated or superposed on its own (genie_motif_potential_grouped) while the placements stay joint; `locate` then also returns
+    'group_rmsd' [B, G] and 'groups' (the labels, by first appearance).  `None` or one label is the single rigid motif above, the same
+    entries and the same results."""
+
+    def __init__(self, segments, n_res, alphas_cumprod, tausq=0.012, max_offsets=1000, rng=None, device='cuda', align='translation',
+                 groups=None):
         from . import capi
         if align not in ('translation', 'rigid'):
             raise ValueError("align must be 'translation' or 'rigid', got %r" % (align,))
         self.align = align
         self.lib = capi.load_library()
+        segs = [torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3) for x in segments]
+        self.seg_len = [len(x) for x in segs]
+        if not segs or min(self.seg_len) < 1:
+            raise ValueError('the motif needs at least one segment of at least one residue')
+        # the motif is validated on the host, once, before the device is looked at and before any placement is drawn
+        self.groups = self.seg_group = None                              # (set for two or more groups)
+        if groups is not None:
+            labels, index = canonical_groups(groups, len(segs))
+            if len(labels) > capi.MOTIF_MAX_GROUPS:
+                raise ValueError('%d motif groups, at most %d are supported' % (len(labels), capi.MOTIF_MAX_GROUPS))
+            if len(labels) > 1:
+                self.groups, self.seg_group = labels, index
+        if align == 'rigid' and self.groups is None:
+            _check_superposable(torch.cat(segs), '')
+        elif align == 'rigid':
+            for g, label in enumerate(self.groups):
+                _check_superposable(torch.cat([x for x, i in zip(segs, self.seg_group) if i == g]), ' in group %r' % (label,))
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise capi.GenieError('MotifPotential runs on the GPU (libgenie_hip); there is no CPU path')
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        segs = [torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3) for x in segments]
-        self.seg_len = [len(x) for x in segs]
-        if not segs or min(self.seg_len) < 1:
-            raise ValueError('the motif needs at least one segment of at least one residue')
-        if align == 'rigid':                                             # (on the host, once, before any placement is drawn)
-            tgt = torch.cat(segs).double()
-            if len(tgt) < 3:
-                raise ValueError('a superposed fit needs at least 3 motif residues, got %d' % len(tgt))
-            sv = torch.linalg.svdvals(tgt - tgt.mean(dim=0, keepdim=True))
-            if float(sv[1]) < 1e-3 * float(sv[0]):
-                raise ValueError('the motif residues are collinear: their superposition has no unique rotation')
         self.n_res, self.tausq = int(n_res), float(tausq)
         self.locs = get_all_motif_locations(self.n_res, self.seg_len, max_offsets, rng)
         if not self.locs:
@@ -285,6 +322,10 @@ class MotifPotential:
         self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
         self._work = torch.zeros(0, dtype=torch.uint8, device=self.device)
         self.has_fit = self.M >= 3                                      # locate() superposes: three residues at least
+        if self.groups is not None:
+            self.G = len(self.groups)
+            self.seg_group_t = torch.tensor(self.seg_group, dtype=torch.int32, device=self.device)
+            self.has_fit = min(sum(n for n, g in zip(self.seg_len, self.seg_group) if g == k) for k in range(self.G)) >= 3
         self._one = torch.ones(1, dtype=torch.float32, device=self.device)
 
     def variance(self, step):
@@ -297,12 +338,21 @@ class MotifPotential:
         """Where the motif is in x [B,N,3]: {'best' [B]: the placement that fits best after optimal superposition (the lowest
         index of equal ones), 'rmsd' [B]: its motif RMSD, 'starts', 'ends' [B,S]: the residues its segments occupy, 0-based, end
         inclusive (what the reference writes to motif_location.txt, unconditional_smc.py:334-343)}.  Always the superposed fit,
-        whatever `align` guides with; tensors on the potential's device."""
+        whatever `align` guides with; tensors on the potential's device.  With motif groups every group is superposed on its own:
+        'rmsd' is over all motif residues, and 'group_rmsd' [B, G] and 'groups' (the labels, in that order) are added."""
         if not self.has_fit:
+            if self.groups is not None:
+                raise ValueError('a superposed fit needs at least 3 motif residues in every group')
             raise ValueError('a superposed fit needs at least 3 motif residues, got %d' % self.M)
-        best, rmsd = self._launch_rigid(self._checked(x), self._one, fit=True)     # (argmax of -q/2: var plays no part)
+        if self.groups is not None:
+            best, rmsd, group_rmsd = self._launch_grouped(self._checked(x), self._one, fit=True, rigid=True)
+        else:
+            best, rmsd = self._launch_rigid(self._checked(x), self._one, fit=True)     # (argmax of -q/2: var plays no part)
         starts = self.starts[best.long()].long()
-        return {'best': best.long(), 'rmsd': rmsd, 'starts': starts, 'ends': starts + self.seg_len_t.long()[None] - 1}
+        fit = {'best': best.long(), 'rmsd': rmsd, 'starts': starts, 'ends': starts + self.seg_len_t.long()[None] - 1}
+        if self.groups is not None:
+            fit.update(group_rmsd=group_rmsd, groups=list(self.groups))
+        return fit
 
     def _checked(self, x0):
         if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
@@ -314,6 +364,8 @@ class MotifPotential:
     def _launch(self, x0, var):
         import ctypes as C
         x = self._checked(x0)
+        if self.groups is not None:
+            return self._launch_grouped(x, var, fit=False, rigid=self.align == 'rigid')
         if self.align == 'rigid':
             return self._launch_rigid(x, var, fit=False)
         B = x.shape[0]
@@ -355,3 +407,29 @@ class MotifPotential:
             from . import capi
             raise capi.GenieError('genie_motif_potential_rigid failed (%d)' % rc)
         return a, b
+
+    def _launch_grouped(self, x, var, fit, rigid):
+        """genie_motif_potential_grouped on x (f32, contiguous): (best, rmsd, group_rmsd) when `fit`, else (logp, grad)."""
+        import ctypes as C
+        B, align = x.shape[0], int(bool(rigid))
+        need = self.lib.genie_motif_potential_grouped_work_bytes(B, self.P, self.G, align)
+        if need > self._work.numel():
+            self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
+        null = C.c_void_p(0)
+        p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
+        if fit:
+            out = (torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, dtype=torch.float32, device=x.device),
+                   torch.empty(B, self.G, dtype=torch.float32, device=x.device))
+            outs = (null, null, p(out[0]), p(out[1]), p(out[2]))
+        else:
+            out = (torch.empty(B, dtype=torch.float32, device=x.device), torch.empty_like(x))
+            outs = (p(out[0]), p(out[1]), null, null, null)
+        with torch.cuda.device(x.device):
+            rc = self.lib.genie_motif_potential_grouped(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
+                                                        self.P, self.S, self.M, self.G, p(self.seg_len_t), p(self.seg_group_t),
+                                                        p(self.starts), p(self.target), p(var), align, *outs,
+                                                        p(self._work) if need else null, self._work.numel())
+        if rc != 0:
+            from . import capi
+            raise capi.GenieError('genie_motif_potential_grouped failed (%d)' % rc)
+        return out

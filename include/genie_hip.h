@@ -177,6 +177,36 @@ int genie_motif_potential_rigid(genie_stream_t stream, int B, int N, const float
                                 int32_t* best_out /*[B] or NULL*/, float* rmsd_out /*[B] or NULL*/, void* work, size_t work_bytes);
 size_t genie_motif_potential_rigid_work_bytes(int B, int P);
 
+/* The same potential for a multi-motif problem: segment s belongs to motif group seg_group[s] in 0..G-1 (every group non-empty,
+ * numbered by first appearance in segment order; a group's segments need not be adjacent).  The segments of one group keep their
+ * relative pose; different groups are independent bodies, so every group is compared on its own, translated (align 0) or superposed
+ * (align 1).  Placements stay joint: all segments in order, without overlap, one softmax over p.  For group g with M_g residues,
+ * m running over its motif positions:
+ *   c^g_bp(m) = x0[b, r_p(m)] - mean_{m in g} x0[b, r_p(m)],   t^g(m) = target[m] - mean_{m in g} target[m]   (centred here, per group)
+ *   e^g_bp(m) = c^g_bp(m) - R^g_bp t^g(m),   R^g = I (align 0) or argmin over proper rotations of sum_{m in g} |c^g - R t^g|^2 (align 1)
+ *   q^g_bp = sum_{m in g} |e^g_bp(m)|^2 (from the residuals),   q_bp = sum_g q^g_bp,   score[b,p] = -q_bp / (2 var)
+ *   logp_out[b] = logsumexp_p score[b,p] - log P,   grad_out[b,n] = -sum_p w_bp [n in p] e^{g(n)}_bp(m_p(n)) / var,  w = softmax_p score
+ * (exactly 0 at residues no placement covers),
+ *   best_out[b] = the lowest p with the largest score,   rmsd_out[b] = sqrt(q_{b,best} / M),
+ *   group_rmsd_out[b,g] = sqrt(q^g_{b,best} / M_g): every group's own RMSD in that placement.
+ * With G = 1 this is genie_motif_potential (of a centred target) or genie_motif_potential_rigid, to rounding.
+ * logp_out and grad_out are given together or both NULL; best_out, rmsd_out, group_rmsd_out may each be NULL; at least one output is
+ * asked for; without a gradient one work-group per particle runs.  A placement's record is per group (16 B per group, 32 B with a
+ * rotation, plus 4 B per placement): records stay in LDS up to 96 KiB of them -- 1445 placements of 2 superposed groups, 378 of
+ * GENIE_MOTIF_MAX_GROUPS -- and spill to `work` beyond (genie_motif_potential_grouped_work_bytes(B, P, G, align) bytes, 16-byte
+ * aligned; 0 = none needed), with a second launch.  No allocation, no synchronisation, bitwise reproducible, as above.
+ * Returns -1, before the device is touched, for G < 1, G > GENIE_MOTIF_MAX_GROUPS, G > S, align not 0 or 1, M < 3 G with align 1
+ * (every group needs 3 residues to be superposed: seg_len is device memory, so the caller checks the groups themselves), and for
+ * what genie_motif_potential_rigid refuses. */
+#define GENIE_MOTIF_MAX_GROUPS 8
+int genie_motif_potential_grouped(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int P, int S, int M, int G,
+                                  const int32_t* seg_len /*[S]*/, const int32_t* seg_group /*[S]*/, const int32_t* starts /*[P,S]*/,
+                                  const float* target /*[M,3]*/, const float* var /*[1], device*/, int align /*0 translation, 1 rigid*/,
+                                  float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/, int32_t* best_out /*[B] or NULL*/,
+                                  float* rmsd_out /*[B] or NULL*/, float* group_rmsd_out /*[B,G] or NULL*/, void* work,
+                                  size_t work_bytes);
+size_t genie_motif_potential_grouped_work_bytes(int B, int P, int G, int align);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
