@@ -248,7 +248,7 @@ def _check_starts(starts, seg_len, n_res):
 class _MotifPotentialFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, pot, var):
-        logp, grad = pot._launch(x0, var)
+        logp, grad = pot._launch(pot._checked(x0), var)
         ctx.save_for_backward(grad)
         return logp
 
@@ -344,14 +344,11 @@ class MotifPotential:
             if self.groups is not None:
                 raise ValueError('a superposed fit needs at least 3 motif residues in every group')
             raise ValueError('a superposed fit needs at least 3 motif residues, got %d' % self.M)
-        if self.groups is not None:
-            best, rmsd, group_rmsd = self._launch_grouped(self._checked(x), self._one, fit=True, rigid=True)
-        else:
-            best, rmsd = self._launch_rigid(self._checked(x), self._one, fit=True)     # (argmax of -q/2: var plays no part)
+        best, rmsd, *group_rmsd = self._launch(self._checked(x), self._one, fit=True)      # (argmax of -q/2: var plays no part)
         starts = self.starts[best.long()].long()
         fit = {'best': best.long(), 'rmsd': rmsd, 'starts': starts, 'ends': starts + self.seg_len_t.long()[None] - 1}
         if self.groups is not None:
-            fit.update(group_rmsd=group_rmsd, groups=list(self.groups))
+            fit.update(group_rmsd=group_rmsd[0], groups=list(self.groups))
         return fit
 
     def _checked(self, x0):
@@ -361,75 +358,44 @@ class MotifPotential:
             raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
         return x0.detach().to(torch.float32).contiguous()
 
-    def _launch(self, x0, var):
+    def _entry(self, x, var, fit):
+        """The C entry that (`groups`, `align`, `fit`) select, for x (f32, contiguous): (its name, the `work` bytes it needs, its
+        arguments up to `work`, its outputs).  The outputs are freshly allocated, in the entry's order logp, grad, best, rmsd
+        [, group_rmsd]: the fit when `fit` (always superposed), else the potential; the other half is None and passed as NULL."""
         import ctypes as C
-        x = self._checked(x0)
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        rigid = fit or self.align == 'rigid'
+        head = (C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x), self.P, self.S, self.M)
+        tail = (p(self.starts), p(self.target), p(var))
         if self.groups is not None:
-            return self._launch_grouped(x, var, fit=False, rigid=self.align == 'rigid')
-        if self.align == 'rigid':
-            return self._launch_rigid(x, var, fit=False)
-        B = x.shape[0]
-        need = self.lib.genie_motif_potential_work_bytes(B, self.P)
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
-        logp = torch.empty(B, dtype=torch.float32, device=x.device)
-        grad = torch.empty_like(x)
-        p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
-        with torch.cuda.device(x.device):
-            rc = self.lib.genie_motif_potential(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
-                                                self.P, self.S, self.M, p(self.seg_len_t), p(self.starts), p(self.target), p(var),
-                                                p(logp), p(grad), p(self._work) if need else C.c_void_p(0), self._work.numel())
-        if rc != 0:
-            from . import capi
-            raise capi.GenieError('genie_motif_potential failed (%d)' % rc)
-        return logp, grad
-
-    def _launch_rigid(self, x, var, fit):
-        """genie_motif_potential_rigid on x (f32, contiguous): (best, rmsd) when `fit`, else (logp, grad)."""
-        import ctypes as C
-        B = x.shape[0]
-        need = self.lib.genie_motif_potential_rigid_work_bytes(B, self.P)
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
-        null = C.c_void_p(0)
-        p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
-        if fit:
-            a, b = torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, dtype=torch.float32, device=x.device)
-            outs = (null, null, p(a), p(b))
+            name, n_out = 'genie_motif_potential_grouped', 5
+            need = self.lib.genie_motif_potential_grouped_work_bytes(B, self.P, self.G, int(rigid))
+            args = head + (self.G, p(self.seg_len_t), p(self.seg_group_t)) + tail + (int(rigid),)
+        elif rigid:
+            name, n_out = 'genie_motif_potential_rigid', 4
+            need = self.lib.genie_motif_potential_rigid_work_bytes(B, self.P)
+            args = head + (p(self.seg_len_t),) + tail
         else:
-            a, b = torch.empty(B, dtype=torch.float32, device=x.device), torch.empty_like(x)
-            outs = (p(a), p(b), null, null)
-        with torch.cuda.device(x.device):
-            rc = self.lib.genie_motif_potential_rigid(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
-                                                      self.P, self.S, self.M, p(self.seg_len_t), p(self.starts), p(self.target), p(var),
-                                                      *outs, p(self._work) if need else null, self._work.numel())
-        if rc != 0:
-            from . import capi
-            raise capi.GenieError('genie_motif_potential_rigid failed (%d)' % rc)
-        return a, b
+            name, n_out = 'genie_motif_potential', 2
+            need = self.lib.genie_motif_potential_work_bytes(B, self.P)
+            args = head + (p(self.seg_len_t),) + tail
+        if fit:
+            outs = [None, None, torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, **f32)]
+            outs += [torch.empty(B, self.G, **f32)] if n_out == 5 else []
+        else:
+            outs = [torch.empty(B, **f32), torch.empty_like(x)] + [None] * (n_out - 2)
+        return name, need, args + tuple(p(t) for t in outs), outs
 
-    def _launch_grouped(self, x, var, fit, rigid):
-        """genie_motif_potential_grouped on x (f32, contiguous): (best, rmsd, group_rmsd) when `fit`, else (logp, grad)."""
+    def _launch(self, x, var, fit=False):
+        """One call of the C entry on x (f32, contiguous): (best, rmsd[, group_rmsd]) when `fit`, else (logp, grad)."""
         import ctypes as C
-        B, align = x.shape[0], int(bool(rigid))
-        need = self.lib.genie_motif_potential_grouped_work_bytes(B, self.P, self.G, align)
+        name, need, args, outs = self._entry(x, var, fit)
         if need > self._work.numel():
             self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
-        null = C.c_void_p(0)
-        p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
-        if fit:
-            out = (torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, dtype=torch.float32, device=x.device),
-                   torch.empty(B, self.G, dtype=torch.float32, device=x.device))
-            outs = (null, null, p(out[0]), p(out[1]), p(out[2]))
-        else:
-            out = (torch.empty(B, dtype=torch.float32, device=x.device), torch.empty_like(x))
-            outs = (p(out[0]), p(out[1]), null, null, null)
         with torch.cuda.device(x.device):
-            rc = self.lib.genie_motif_potential_grouped(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
-                                                        self.P, self.S, self.M, self.G, p(self.seg_len_t), p(self.seg_group_t),
-                                                        p(self.starts), p(self.target), p(var), align, *outs,
-                                                        p(self._work) if need else null, self._work.numel())
+            rc = getattr(self.lib, name)(*args, C.c_void_p(self._work.data_ptr() if need else 0), self._work.numel())
         if rc != 0:
             from . import capi
-            raise capi.GenieError('genie_motif_potential_grouped failed (%d)' % rc)
-        return out
+            raise capi.GenieError('%s failed (%d)' % (name, rc))
+        return tuple(t for t in outs if t is not None)

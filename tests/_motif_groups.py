@@ -1,14 +1,11 @@
 """float64 oracle of the group-wise motif potential (genie_motif_potential_grouped, csrc/smc_kernels.hip; include/genie_hip.h states
 the formulas) and the inputs its tests share: per-group selections through `placement_index`, a per-group Kabsch fit (or the identity),
 q summed over the groups, logsumexp over the joint placements, the gradient by torch autograd."""
-import os
-
 import numpy as np
 import torch
 
+from _motif import walk
 from _motif_rigid import centred_selection, placement_index, residual_q
-
-MOTIF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'motif_problem_6E6R.pdb')
 
 
 def canonical(groups):
@@ -70,27 +67,10 @@ def group_fit_rmsd(xyz, starts_row, seg_len, seg_group, target):
 
 # ---- shared inputs -----------------------------------------------------------------------------------------------------------------
 
-def segments_6e6r():
-    from genie2_amd.sample_unconditional_motif import load_motif_segments
-    return [torch.tensor(s, dtype=torch.float32) for s in load_motif_segments(MOTIF)]
-
-
 def segments_343():
     """Three synthetic segments of 3, 4 and 3 residues (4 randn), for groups A, B, A."""
     g = torch.Generator().manual_seed(77)
     return [4 * torch.randn(n, 3, generator=g) for n in (3, 4, 3)]
-
-
-def walk(B, N, seed, step=3.8):
-    """Chain-like coordinates: a random walk of C-alpha spacing."""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.randn(B, N, 3, generator=g)
-    return torch.cumsum(step * v / v.norm(dim=-1, keepdim=True), dim=1)
-
-
-def all_starts(n_res, lens, max_offsets=10 ** 6, seed=0):
-    from genie2_amd.smc import get_all_motif_locations, placement_starts
-    return placement_starts(get_all_motif_locations(n_res, lens, max_offsets, np.random.RandomState(seed)))
 
 
 def random_rotation(g):
@@ -112,9 +92,3 @@ def planted(segs, at=(5, 30), n_res=60, seed=61, mirror=None):
             m = m * torch.tensor([1.0, 1.0, -1.0], dtype=torch.float64)
         x[0, st:st + len(seg)] = m @ r.T + shift
     return x.float()
-
-
-def top_two_gap(score):
-    """Relative gap between the two largest scores of every row [B, P >= 2]."""
-    top = torch.topk(score, 2, dim=1).values
-    return (top[:, 0] - top[:, 1]) / top[:, 0].abs()

@@ -64,9 +64,3 @@ def fit_rmsd(xyz, starts_row, seg_len, target):
     t = torch.as_tensor(target).double()
     c = centred_selection(torch.as_tensor(xyz).double()[None], placement_index(st, seg_len))
     return float(torch.sqrt(residual_q(c, t - t.mean(dim=0, keepdim=True))[0, 0] / t.shape[0]))
-
-
-def top_two_gap(score):
-    """Relative gap between the two largest scores of every row [B, P >= 2]."""
-    top = torch.topk(score, 2, dim=1).values
-    return (top[:, 0] - top[:, 1]) / top[:, 0].abs()

@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 import torch
 
-from _motif_groups import (MOTIF, all_starts, canonical, group_fit_rmsd, grouped_logp_only, grouped_oracle, planted, random_rotation,
-                           segments_343, segments_6e6r, top_two_gap, walk)
+from _motif import (MOTIF, _abar, _ca_coordinates, _check, _fix_var, _lds_cap, _pot, _run, _tiny_model, _var500, all_starts, segments_6e6r,
+                    top_two_gap, walk)
+from _motif_groups import canonical, group_fit_rmsd, grouped_logp_only, grouped_oracle, planted, random_rotation, segments_343
 from _motif_rigid import rigid_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,43 +166,6 @@ def test_motif_potential_validates_its_groups_on_the_host():
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------
 
-def _abar(T=1000):
-    from genie2_amd import pack
-    return pack.schedule_tensors(T)['alphas_cumprod'].cuda()
-
-
-def _var500(abar):
-    from genie2_amd.smc import xstart_variance
-    return float(xstart_variance(abar[500], 0.012).to(torch.float32))      # the f32 value the kernel reads
-
-
-def _fix_var(pot, v):
-    pot.variance = lambda step, v=v: torch.tensor([v], dtype=torch.float32, device='cuda')
-    return float(np.float32(v))
-
-
-def _run(pot, x0, step=500):
-    x = x0.cuda().requires_grad_(True)
-    lp = pot(x, step)
-    g, = torch.autograd.grad(lp.sum(), x)
-    return lp.detach(), g
-
-
-def _check(logp, grad, ref, what, grad_floor=0.0):
-    lp, g = logp.double().cpu(), grad.double().cpu()
-    tol = 1e-5 * ref['logp'].abs().clamp(min=1.0)
-    print(what, 'logp error / bound', ((lp - ref['logp']).abs() / tol).tolist())
-    for b in range(g.shape[0]):
-        d = float((g[b] - ref['grad'][b]).abs().max())
-        bound = 1e-5 * (float(ref['grad'][b].abs().max()) + grad_floor)
-        print(what, 'particle %d: gradient error %.3e, bound %.3e' % (b, d, bound))
-    assert bool(torch.isfinite(lp).all()) and bool(torch.isfinite(g).all()), what
-    assert bool(((lp - ref['logp']).abs() <= tol).all()), (what, lp, ref['logp'])
-    for b in range(g.shape[0]):
-        d = float((g[b] - ref['grad'][b]).abs().max())
-        assert d <= 1e-5 * (float(ref['grad'][b].abs().max()) + grad_floor), (what, b, d)
-
-
 def _check_fit(fit, ref, what):
     gap = top_two_gap(ref['score']) if ref['score'].shape[1] > 1 else torch.ones(ref['score'].shape[0])
     best, rmsd = fit['best'].cpu().long(), fit['rmsd'].double().cpu()
@@ -214,11 +178,6 @@ def _check_fit(fit, ref, what):
         print(what, 'group rmsd', gr.tolist(), ref['group_rmsd'].tolist())
         assert gr.shape == ref['group_rmsd'].shape
         assert bool(((gr - ref['group_rmsd']).abs() <= 1e-5 * ref['group_rmsd'] + 1e-4).all()), (what, gr, ref['group_rmsd'])
-
-
-def _pot(segs, n_res, abar, P=10 ** 6, seed=0, **kw):
-    from genie2_amd.smc import MotifPotential
-    return MotifPotential(segs, n_res, abar, max_offsets=P, rng=np.random.RandomState(seed), device='cuda', **kw)
 
 
 def _entry(pot, seg_group, x, var, align, want_potential=True, want_fit=True):
@@ -339,20 +298,6 @@ def test_groups_of_separate_segments_and_of_three_residues_n24(labels, align):
         _check_fit(pot.locate(x0.cuda()), ref, labels)
 
 
-def _lds_cap(lib, B, G, align):
-    """The largest P whose records stay in LDS (work_bytes == 0), by bisection on the host function."""
-    lo, hi = 1, 20000
-    assert lib.genie_motif_potential_grouped_work_bytes(B, lo, G, align) == 0
-    assert lib.genie_motif_potential_grouped_work_bytes(B, hi, G, align) > 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if lib.genie_motif_potential_grouped_work_bytes(B, mid, G, align) == 0:
-            lo = mid
-        else:
-            hi = mid
-    return lo
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('align', ['rigid', 'translation'])
 @pytest.mark.parametrize('which', ['cap', 'cap+1'])
@@ -363,7 +308,7 @@ def test_two_groups_match_the_float64_oracle_around_the_lds_cap(which, align):
     lens = [len(s) for s in segs]
     var = _var500(abar)
     a = int(align == 'rigid')
-    cap = _lds_cap(capi.load_library(), 2, 2, a)
+    cap = _lds_cap(lambda P: capi.load_library().genie_motif_potential_grouped_work_bytes(2, P, 2, a))
     P = cap + (which == 'cap+1')
     pot = _pot(segs, 256, abar, P=P, seed=22, align=align, groups=['A', 'B'])
     assert pot.P == P and (pot.lib.genie_motif_potential_grouped_work_bytes(2, P, 2, a) > 0) == (which != 'cap')
@@ -498,16 +443,6 @@ def test_locate_needs_three_residues_in_every_group():
     assert bool(torch.isfinite(lp).all()) and bool(torch.isfinite(g).all())
 
 
-def _tiny_model(base_weights, T=12):
-    from genie.config import Config
-    from genie2_amd.diffusion import Genie
-    cfg = Config()
-    cfg.diffusion['n_timestep'] = T
-    model = Genie(cfg)
-    model.model.load_state_dict(base_weights)
-    return model.eval().to('cuda:0')
-
-
 @pytest.mark.gpu
 def test_grouped_guidance_pulls_both_motifs_in_and_the_sampler_reports_every_group(tmp_path, base_weights):
     """No numeric bar is set for the pull: the guided mean RMSD has to be below the unguided one on identical noise, and the ratio is
@@ -545,11 +480,6 @@ def test_grouped_guidance_pulls_both_motifs_in_and_the_sampler_reports_every_gro
           % (fit['rmsd'].tolist(), float(fit['rmsd'].mean()), rmsd_free.tolist(), float(rmsd_free.mean()),
              float(fit['rmsd'].mean()) / float(rmsd_free.mean())))
     assert float(fit['rmsd'].mean()) < float(rmsd_free.mean())
-
-
-def _ca_coordinates(path):
-    ca = [line for line in open(path) if line.startswith('ATOM') and line[13:15].strip() == 'CA']
-    return np.array([[float(line[30:38]), float(line[38:46]), float(line[46:54])] for line in ca])
 
 
 @pytest.mark.gpu

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from _motif import _abar, _tiny_model, segments_6e6r as _segments, walk as _walk
 from conftest import GOLDEN
 
 MOTIF = os.path.join(GOLDEN, 'motif_problem_6E6R.pdb')
@@ -22,11 +23,6 @@ def _masks_from_starts(starts, seg_len, n_res):
         for st, n in zip(row, seg_len):
             m[p, st:st + n] = True
     return m
-
-
-def _segments():
-    from genie2_amd.sample_unconditional_motif import load_motif_segments
-    return [torch.tensor(s, dtype=torch.float32) for s in load_motif_segments(MOTIF)]
 
 
 # ---- CPU -------------------------------------------------------------------------------------------------------------------------
@@ -108,13 +104,6 @@ def test_motif_cli_parser_segments_and_tasks(capsys):
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------
 
-def _walk(B, N, seed, step=3.8):
-    """Chain-like coordinates: a random walk of C-alpha spacing."""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.randn(B, N, 3, generator=g)
-    return torch.cumsum(step * v / v.norm(dim=-1, keepdim=True), dim=1)
-
-
 def _reference(x0, starts, seg_len, target, var):
     """float64 restatement of motif_twisting_function for a given var, vectorised over placements (its equality with
     motif_twisting_function itself is checked below), with the gradient from torch autograd."""
@@ -136,11 +125,6 @@ def _check(logp, grad, ref_logp, ref_grad, what):
         d = float((g[b] - ref_grad[b]).abs().max())
         bound = 1e-5 * float(ref_grad[b].abs().max())
         assert d <= bound, (what, b, d, bound)
-
-
-def _abar(T=1000):
-    from genie2_amd import pack
-    return pack.schedule_tensors(T)['alphas_cumprod'].cuda()
 
 
 def pot_var(abar, step, tausq=0.012):
@@ -239,16 +223,6 @@ def test_fused_potential_is_deterministic_and_never_synchronises():
     outside = torch.ones(10, dtype=torch.bool)
     outside[st:st + 3] = False
     assert bool((g[:, outside] == 0).all()) and bool((g[:, ~outside] != 0).any())
-
-
-def _tiny_model(base_weights, T=12):
-    from genie.config import Config
-    from genie2_amd.diffusion import Genie
-    cfg = Config()
-    cfg.diffusion['n_timestep'] = T
-    model = Genie(cfg)
-    model.model.load_state_dict(base_weights)
-    return model.eval().to('cuda:0')
 
 
 @pytest.mark.gpu

@@ -13,33 +13,18 @@ import numpy as np
 import pytest
 import torch
 
-from _motif_rigid import fit_rmsd, logp_only, rigid_oracle, top_two_gap
+from _motif import (_abar, _ca_coordinates, _check, _fix_var, _lds_cap, _pot, _run, _tiny_model, _var500, all_starts as _all_starts,
+                    segments_6e6r as _segments, top_two_gap, walk as _walk)
+from _motif_rigid import fit_rmsd, logp_only, rigid_oracle
 from conftest import GOLDEN
 
 MOTIF = os.path.join(GOLDEN, 'motif_problem_6E6R.pdb')
 _ORACLE = {}
 
 
-def _segments():
-    from genie2_amd.sample_unconditional_motif import load_motif_segments
-    return [torch.tensor(s, dtype=torch.float32) for s in load_motif_segments(MOTIF)]
-
-
 def _target():
     t = torch.cat(_segments())
     return t - t.mean(dim=0, keepdim=True)
-
-
-def _walk(B, N, seed, step=3.8):
-    """Chain-like coordinates: a random walk of C-alpha spacing."""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.randn(B, N, 3, generator=g)
-    return torch.cumsum(step * v / v.norm(dim=-1, keepdim=True), dim=1)
-
-
-def _all_starts(n_res, lens, max_offsets=10 ** 6, seed=0):
-    from genie2_amd.smc import get_all_motif_locations, placement_starts
-    return placement_starts(get_all_motif_locations(n_res, lens, max_offsets, np.random.RandomState(seed)))
 
 
 def _oracle(key, x0, starts, lens, target, var, **kw):
@@ -117,43 +102,6 @@ def test_motif_cli_parser_has_the_alignment_and_location_flags():
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------
 
-def _abar(T=1000):
-    from genie2_amd import pack
-    return pack.schedule_tensors(T)['alphas_cumprod'].cuda()
-
-
-def _var500(abar):
-    from genie2_amd.smc import xstart_variance
-    return float(xstart_variance(abar[500], 0.012).to(torch.float32))      # the f32 value the kernel reads
-
-
-def _fix_var(pot, v):
-    pot.variance = lambda step, v=v: torch.tensor([v], dtype=torch.float32, device='cuda')
-    return float(np.float32(v))
-
-
-def _run(pot, x0, step=500):
-    x = x0.cuda().requires_grad_(True)
-    lp = pot(x, step)
-    g, = torch.autograd.grad(lp.sum(), x)
-    return lp.detach(), g
-
-
-def _check(logp, grad, ref, what, grad_floor=0.0):
-    lp, g = logp.double().cpu(), grad.double().cpu()
-    tol = 1e-5 * ref['logp'].abs().clamp(min=1.0)
-    print(what, 'logp error / bound', ((lp - ref['logp']).abs() / tol).tolist())
-    for b in range(g.shape[0]):
-        d = float((g[b] - ref['grad'][b]).abs().max())
-        bound = 1e-5 * (float(ref['grad'][b].abs().max()) + grad_floor)
-        print(what, 'particle %d: gradient error %.3e, bound %.3e' % (b, d, bound))
-    assert bool(torch.isfinite(lp).all()) and bool(torch.isfinite(g).all()), what
-    assert bool(((lp - ref['logp']).abs() <= tol).all()), (what, lp, ref['logp'])
-    for b in range(g.shape[0]):
-        d = float((g[b] - ref['grad'][b]).abs().max())
-        assert d <= 1e-5 * (float(ref['grad'][b].abs().max()) + grad_floor), (what, b, d)
-
-
 def _check_fit(fit, ref, what, need_gap=True):
     gap = top_two_gap(ref['score']) if ref['score'].shape[1] > 1 else torch.ones(ref['score'].shape[0])
     best, rmsd = fit['best'].cpu().long(), fit['rmsd'].double().cpu()
@@ -162,24 +110,6 @@ def _check_fit(fit, ref, what, need_gap=True):
         assert bool((gap > 1e-4).all()), (what, gap)                 # the argmax is the oracle's to decide
         assert torch.equal(best, ref['best']), (what, best, ref['best'])
     assert bool(((rmsd - ref['rmsd']).abs() <= 1e-5 * ref['rmsd'] + 1e-4).all()), (what, rmsd, ref['rmsd'])
-
-
-def _pot(segs, n_res, abar, P=10 ** 6, seed=0, **kw):
-    from genie2_amd.smc import MotifPotential
-    return MotifPotential(segs, n_res, abar, max_offsets=P, rng=np.random.RandomState(seed), device='cuda', **kw)
-
-
-def _lds_cap(lib, B):
-    """The largest P whose records stay in LDS (work_bytes == 0), by bisection on the host function."""
-    lo, hi = 1, 20000
-    assert lib.genie_motif_potential_rigid_work_bytes(B, lo) == 0 and lib.genie_motif_potential_rigid_work_bytes(B, hi) > 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if lib.genie_motif_potential_rigid_work_bytes(B, mid) == 0:
-            lo = mid
-        else:
-            hi = mid
-    return lo
 
 
 @pytest.mark.gpu
@@ -248,7 +178,7 @@ def test_rigid_potential_matches_the_float64_oracle_around_the_lds_cap(which):
     segs = _segments()
     lens = [len(s) for s in segs]
     var = _var500(abar)
-    cap = _lds_cap(capi.load_library(), 2)
+    cap = _lds_cap(lambda P: capi.load_library().genie_motif_potential_rigid_work_bytes(2, P))
     P = {'cap': cap, 'cap+1': cap + 1, '20000': 20000}[which]
     pot = _pot(segs, 256, abar, P=P, seed=22, align='rigid')
     assert pot.P == P and (pot.lib.genie_motif_potential_rigid_work_bytes(2, P) > 0) == (which != 'cap')
@@ -433,16 +363,6 @@ def test_align_translation_is_todays_potential_and_rigid_validates_its_motif():
     MotifPotential([torch.tensor([[0.0, 0.0, 0.0], [3.8, 0.0, 0.0]])], 10, abar, device='cuda')
 
 
-def _tiny_model(base_weights, T=12):
-    from genie.config import Config
-    from genie2_amd.diffusion import Genie
-    cfg = Config()
-    cfg.diffusion['n_timestep'] = T
-    model = Genie(cfg)
-    model.model.load_state_dict(base_weights)
-    return model.eval().to('cuda:0')
-
-
 @pytest.mark.gpu
 def test_rigid_guidance_pulls_the_motif_in_and_the_sampler_reports_where(tmp_path, base_weights):
     from genie2_amd import pack
@@ -477,11 +397,6 @@ def test_rigid_guidance_pulls_the_motif_in_and_the_sampler_reports_where(tmp_pat
     print('superposed motif RMSD: guided %s (mean %.3f), unguided %s (mean %.3f)'
           % (fit['rmsd'].tolist(), float(fit['rmsd'].mean()), rmsd_free.tolist(), float(rmsd_free.mean())))
     assert float(fit['rmsd'].mean()) <= 0.5 * float(rmsd_free.mean())
-
-
-def _ca_coordinates(path):
-    ca = [line for line in open(path) if line.startswith('ATOM') and line[13:15].strip() == 'CA']
-    return np.array([[float(line[30:38]), float(line[38:46]), float(line[46:54])] for line in ca])
 
 
 @pytest.mark.gpu

@@ -35,35 +35,14 @@ def median_ms(fn, reps, warmup, batch=20):
 
 
 def entry_call(pot, x, var, fit):
-    """A zero-argument launch of the C entry `pot` uses, with its outputs allocated once."""
+    """A zero-argument launch of the C entry `pot` uses (MotifPotential._entry), with its outputs allocated once."""
     import ctypes as C
-    import torch
-    B = x.shape[0]
-    p = lambda t: C.c_void_p(t.data_ptr())                      # noqa: E731
-    null, stream = C.c_void_p(0), C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    logp, grad = torch.empty(B, device=x.device), torch.empty_like(x)
-    best, rmsd = torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, device=x.device)
-    head = (stream, B, pot.n_res, p(x), pot.P, pot.S, pot.M)
-    keep = [logp, grad, best, rmsd]
-    if pot.groups is not None:
-        align = int(fit or pot.align == 'rigid')
-        grmsd = torch.empty(B, pot.G, device=x.device)
-        need = pot.lib.genie_motif_potential_grouped_work_bytes(B, pot.P, pot.G, align)
-        outs = (null, null, p(best), p(rmsd), p(grmsd)) if fit else (p(logp), p(grad), null, null, null)
-        fn, tail = pot.lib.genie_motif_potential_grouped, (pot.G, p(pot.seg_len_t), p(pot.seg_group_t), p(pot.starts), p(pot.target), p(var),
-                                                          align) + outs
-        keep.append(grmsd)
-    elif fit or pot.align == 'rigid':
-        need = pot.lib.genie_motif_potential_rigid_work_bytes(B, pot.P)
-        outs = (null, null, p(best), p(rmsd)) if fit else (p(logp), p(grad), null, null)
-        fn, tail = pot.lib.genie_motif_potential_rigid, (p(pot.seg_len_t), p(pot.starts), p(pot.target), p(var)) + outs
-    else:
-        need = pot.lib.genie_motif_potential_work_bytes(B, pot.P)
-        fn, tail = pot.lib.genie_motif_potential, (p(pot.seg_len_t), p(pot.starts), p(pot.target), p(var), p(logp), p(grad))
+    name, need, args, outs = pot._entry(x, var, fit)
     assert need == 0                                            # (P = 1000: every record stays in LDS, one launch per call)
+    fn, null = getattr(pot.lib, name), C.c_void_p(0)
 
-    def launch(keep=keep):
-        rc = fn(*head, *tail, null, 0)
+    def launch(keep=outs):
+        rc = fn(*args, null, 0)
         assert rc == 0
     return launch
 
