@@ -84,6 +84,10 @@ SYMBOLS = {
                                  C.c_void_p]),
     'genie_sample_loop': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    'genie_reverse_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    'genie_sample_loop_steps': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'genie_set_math': (C.c_int, [C.c_void_p, C.c_int]),
     'genie_get_math': (C.c_int, [C.c_void_p]),
     'genie_profile_enable': (C.c_int, [C.c_void_p, C.c_int]),

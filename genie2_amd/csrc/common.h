@@ -315,6 +315,8 @@ void launch_bb_update(genie_ctx* h, hipStream_t st, const StructLayerW& w, const
                       float* z_out);
 void launch_frenet(genie_ctx* h, hipStream_t st, int mode, int step, float scale, float* trans,
                    float* rots, const float* z, const float* eps);
+void launch_reverse_step(genie_ctx* h, hipStream_t st, float a, float bz, float c_scaled, float* trans, float* rots, const float* z,
+                         const float* eps);
 void launch_fill_i32(genie_ctx* h, hipStream_t st, int32_t* p, int n, int v);
 void train_ws_free(genie_ctx* h);
 

@@ -853,6 +853,58 @@ int genie_sample_loop(genie_handle_t h, genie_stream_t stream, float scale, cons
     return GENIE_OK;
 }
 
+// genie_p_sample with the step's coefficients given instead of looked up: any pair of timesteps, either sampler
+int genie_reverse_step(genie_handle_t h, genie_stream_t stream, float a, float bz, float c_scaled, float* trans_inout, float* rots_out,
+                       const float* z, const float* eps) {
+    if (int rc = check_ready(h, "genie_reverse_step")) return rc;
+    if (!trans_inout || !rots_out || !z) { SET_ERR(h, "genie_reverse_step: null tensor"); return GENIE_E_ARG; }
+    if (!std::isfinite(a) || !std::isfinite(bz) || !std::isfinite(c_scaled)) {
+        SET_ERR(h, "genie_reverse_step: non-finite coefficient (a = %g, bz = %g, c_scaled = %g)", a, bz, c_scaled);
+        return GENIE_E_ARG;
+    }
+    launch_reverse_step(h, (hipStream_t)stream, a, bz, c_scaled, trans_inout, rots_out, z, eps);
+    HIP_TRY(h, hipGetLastError());
+    return GENIE_OK;
+}
+
+// genie_sample_loop over a sub-sequence of the timesteps: the same body, the step's scalars from `coef` instead of the schedule table
+int genie_sample_loop_steps(genie_handle_t h, genie_stream_t stream, int n_iter, const int32_t* steps, const float* coef, const float* noise,
+                            const int8_t* quat_codes, int start_from_noise, float* trans_io, float* rots_io, float* record) {
+    if (int rc = check_ready(h, "genie_sample_loop_steps")) return rc;
+    const int T = h->d.n_timestep;
+    if (n_iter < 1) { SET_ERR(h, "genie_sample_loop_steps: n_iter = %d, needs at least 1", n_iter); return GENIE_E_ARG; }
+    if (!steps || !coef || !trans_io || !rots_io) { SET_ERR(h, "genie_sample_loop_steps: null steps, coef, trans_io or rots_io"); return GENIE_E_ARG; }
+    if (!noise && (start_from_noise || n_iter > 1)) {
+        SET_ERR(h, "genie_sample_loop_steps: null noise (needed for the initial state and for every iteration but the last)");
+        return GENIE_E_ARG;
+    }
+    for (int i = 0; i < n_iter; ++i) {
+        if (steps[i] < 1 || steps[i] > T) { SET_ERR(h, "genie_sample_loop_steps: steps[%d] = %d outside 1..%d", i, steps[i], T); return GENIE_E_ARG; }
+        if (i && steps[i] >= steps[i - 1]) {
+            SET_ERR(h, "genie_sample_loop_steps: steps not strictly decreasing (steps[%d] = %d after %d)", i, steps[i], steps[i - 1]);
+            return GENIE_E_ARG;
+        }
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(coef[3 * i + k])) { SET_ERR(h, "genie_sample_loop_steps: non-finite coefficient coef[%d][%d]", i, k); return GENIE_E_ARG; }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n3 = (size_t)h->B * h->N * 3, nn = (size_t)h->B * h->N * h->N;
+    if (start_from_noise) {
+        HIP_TRY(h, hipMemcpyAsync(trans_io, noise, n3 * 4, hipMemcpyDeviceToDevice, st));
+        launch_frenet(h, st, 0, 0, 0.f, trans_io, rots_io, nullptr, nullptr);
+    }
+    for (int it = 0; it < n_iter; ++it) {
+        launch_fill_i32(h, st, h->tsteps, h->B, steps[it]);
+        const int8_t* codes = quat_codes ? quat_codes + (size_t)it * nn : nullptr;
+        if (int rc = denoise_internal(h, st, trans_io, rots_io, h->tsteps, codes, h->loop_z, nullptr)) return rc;
+        const float* eps = (it == n_iter - 1) ? nullptr : noise + (size_t)(it + 1) * n3;
+        launch_reverse_step(h, st, coef[3 * it], coef[3 * it + 1], coef[3 * it + 2], trans_io, rots_io, h->loop_z, eps);
+        if (record) HIP_TRY(h, hipMemcpyAsync(record + (size_t)it * n3, trans_io, n3 * 4, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(h, hipGetLastError());
+    return GENIE_OK;
+}
+
 // ------------------------------------------------------------------ arithmetic
 int genie_set_math(genie_handle_t h, int mode) {
     if (!h || (mode != GENIE_MATH_F32 && mode != GENIE_MATH_HX)) return GENIE_E_ARG;

@@ -1124,6 +1124,9 @@ __global__ __launch_bounds__(NW * 64) void k_struct_rows_hx(
 // (sampler/base.py:249-282, utils/geo_utils.py:21-85).
 //   mode 0: frames of `trans` only.
 //   mode 1: trans <- ((trans - w_z z)/sqrt(alpha_t)) * mask [+ scale sqrt(beta_t) eps, * mask], then frames.
+//   mode 2: trans <- ((a trans + bz z) * mask [+ c_scaled eps]) * mask, then frames: the step in coefficient form, for a jump
+//           from t to any s < t and for DDIM (pack.reverse_coefficients; c_scaled = scale * C).  Mode 1 is its case
+//           a = 1/sqrt(alpha_t), bz = -w_z/sqrt(alpha_t), c_scaled = scale sqrt(beta_t), kept as it was written.
 // Chain starts/ends copy their neighbour exactly as the reference's two
 // sequential fix-up loops do (including what they do for consecutive chain ends).
 // Dynamic LDS: x[N][3] | tv[N][3] | base[N][9] | st1[N][9] | flags.
@@ -1132,7 +1135,7 @@ __global__ __launch_bounds__(256) void k_p_sample_frenet(int mode, float* __rest
                                                          const float* __restrict__ z, const float* __restrict__ eps,
                                                          const int32_t* __restrict__ rmask, const int32_t* __restrict__ cidx,
                                                          int N, float alpha, float sqrt_alpha, float somac, float sqrt_beta,
-                                                         float scale) {
+                                                         float scale, float a, float bz, float c_scaled) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* x = sm;
     float* tv = x + 3 * N;
@@ -1154,6 +1157,15 @@ __global__ __launch_bounds__(256) void k_p_sample_frenet(int mode, float* __rest
             float v = inv_sa * (tr[u] - w_z * z[(size_t)b * N * 3 + u]);
             v = v * m;
             if (eps) { v = v + scale * sqrt_beta * eps[(size_t)b * N * 3 + u]; v = v * m; }
+            x[u] = v;
+            tr[u] = v;
+        }
+    } else if (mode == 2) {
+        for (int u = tid; u < 3 * N; u += 256) {
+            const float m = (float)rmask[b * N + u / 3];
+            float v = a * tr[u] + bz * z[(size_t)b * N * 3 + u];
+            v = v * m;
+            if (eps) { v = v + c_scaled * eps[(size_t)b * N * 3 + u]; v = v * m; }
             x[u] = v;
             tr[u] = v;
         }
@@ -1891,7 +1903,16 @@ void launch_frenet(genie_ctx* h, hipStream_t st, int mode, int step, float scale
     }
     const size_t lds = (size_t)(3 + 3 + 9 + 9) * h->N * sizeof(float);
     hipLaunchKernelGGL(k_p_sample_frenet, dim3(h->B), dim3(256), lds, st, mode, trans, rots, z, eps, h->f_rmask, h->f_cidx, h->N,
-                       al, sa, so, sb, scale);
+                       al, sa, so, sb, scale, 0.f, 0.f, 0.f);
+}
+
+// the step in coefficient form (mode 2 of k_p_sample_frenet): generalises launch_frenet's mode 1 to any pair of timesteps
+void launch_reverse_step(genie_ctx* h, hipStream_t st, float a, float bz, float c_scaled, float* trans, float* rots, const float* z,
+                         const float* eps) {
+    ProfScope ps(h, st, KC_P_SAMPLE);
+    const size_t lds = (size_t)(3 + 3 + 9 + 9) * h->N * sizeof(float);
+    hipLaunchKernelGGL(k_p_sample_frenet, dim3(h->B), dim3(256), lds, st, 2, trans, rots, z, eps, h->f_rmask, h->f_cidx, h->N,
+                       1.f, 1.f, 1.f, 0.f, 0.f, a, bz, c_scaled);
 }
 
 // handle-free form: compute_frenet_frames(coords, chains, mask) of genie/utils/geo_utils.py:21-85 as the reference calls it
@@ -1903,7 +1924,7 @@ int genie_frenet_frames(genie_stream_t stream, int B, int N, const float* coords
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_p_sample_frenet), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_p_sample_frenet, dim3(B), dim3(256), lds, (hipStream_t)stream, 0, const_cast<float*>(coords), rots_out,
-                       (const float*)nullptr, (const float*)nullptr, mask, chains, N, 1.f, 1.f, 1.f, 0.f, 0.f);
+                       (const float*)nullptr, (const float*)nullptr, mask, chains, N, 1.f, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f);
     return hipGetLastError() == hipSuccess ? GENIE_OK : GENIE_E_HIP;
 }
 

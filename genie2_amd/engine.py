@@ -241,6 +241,43 @@ class GenieEngine:
         capi.check(self._h, rc, 'genie_sample_loop')
         return trans, rots, rec
 
+    def reverse_step(self, coef_row, scale, trans, z, eps):
+        """p_sample in coefficient form: `coef_row` = (A, Bz, C), one row of pack.reverse_coefficients; eps None = no noise.
+        In place on `trans`; returns the new frames."""
+        a, bz, c = (float(v) for v in coef_row)
+        rots = torch.empty(self.B, self.N, 3, 3, device=self.device)
+        rc = self.lib.genie_reverse_step(self._h, self._stream(), a, bz, float(scale) * c, _ptr(trans), _ptr(rots), _ptr(z), _ptr(eps))
+        capi.check(self._h, rc, 'genie_reverse_step')
+        return rots
+
+    def sample_loop_steps(self, noise, scale, steps, coef, quat_codes=None, state=None, record=False):
+        """sample_loop over the timesteps `steps` (strictly decreasing) with the rows `coef` [len(steps), 3] of
+        pack.reverse_coefficients.  noise [len(steps),B,N,3] on device: noise[0] the initial trans, noise[k] the draw of iteration
+        k - 1.  With state = (trans, rots) the loop goes on from it (in place) and noise[0] is not read: pass the tails of steps,
+        coef, noise and quat_codes from the first iteration still to run.  Returns (trans, rots, record or None)."""
+        steps = [int(s) for s in steps]
+        K = len(steps)
+        coef = torch.as_tensor(coef, dtype=torch.float64).reshape(-1, 3)
+        if coef.shape[0] != K:
+            raise ValueError('coef has %d rows for %d steps' % (coef.shape[0], K))
+        if noise is None or noise.dim() != 4 or noise.shape[0] != K:
+            raise ValueError('noise must be [%d, B, N, 3], got %s' % (K, None if noise is None else tuple(noise.shape)))
+        noise = self._dev(noise, torch.float32)
+        codes = self._dev(quat_codes, torch.int8) if quat_codes is not None else None
+        if state is None:
+            trans = torch.empty(self.B, self.N, 3, device=self.device)
+            rots = torch.empty(self.B, self.N, 3, 3, device=self.device)
+        else:
+            trans, rots = state
+        rec = torch.empty(K, self.B, self.N, 3, device=self.device) if record else None
+        c_steps = (C.c_int32 * max(K, 1))(*steps)
+        scaled = (coef * torch.tensor([1.0, 1.0, float(scale)], dtype=torch.float64)).flatten().tolist()
+        c_coef = (C.c_float * max(3 * K, 1))(*scaled)
+        rc = self.lib.genie_sample_loop_steps(self._h, self._stream(), K, c_steps, c_coef, _ptr(noise), _ptr(codes),
+                                              1 if state is None else 0, _ptr(trans), _ptr(rots), _ptr(rec))
+        capi.check(self._h, rc, 'genie_sample_loop_steps')
+        return trans, rots, rec
+
     # ------------------------------------------------------------------
     def profile(self, enable):
         self.lib.genie_profile_enable(self._h, 1 if enable else 0)

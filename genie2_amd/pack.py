@@ -156,6 +156,82 @@ def schedule_block(sched):
                         sched['sqrt_betas']]).float().contiguous()
 
 
+SAMPLERS = ('ancestral', 'ddim')
+
+
+def respaced_steps(n_timestep, num_steps):
+    """The timesteps a `num_steps`-step reverse process visits, strictly decreasing: rint(linspace(T, 1, K)), [T] for K = 1,
+    and T, T-1, ..., 1 for K = T."""
+    T, K = int(n_timestep), int(num_steps)
+    if K != num_steps or not 1 <= K <= T:
+        raise ValueError('num_steps must be an integer in 1..%d, got %r' % (T, num_steps))
+    if K == 1:
+        return [T]
+    return [int(v) for v in torch.round(torch.linspace(T, 1, K, dtype=torch.float64)).tolist()]
+
+
+def check_sampler(sampler, eta=None):
+    """The (sampler, eta) pair of the few-step samplers: eta belongs to 'ddim' alone, in [0, 1]; None is its default 0."""
+    if sampler not in SAMPLERS:
+        raise ValueError('sampler must be one of %s, got %r' % (', '.join(map(repr, SAMPLERS)), sampler))
+    if eta is None:
+        return 0.0
+    if sampler == 'ancestral':
+        raise ValueError("eta belongs to the 'ddim' sampler, got eta=%r with 'ancestral'" % (eta,))
+    if not 0.0 <= float(eta) <= 1.0:          # (False for NaN)
+        raise ValueError('eta must be in [0, 1], got %r' % (eta,))
+    return float(eta)
+
+
+def alphas_cumprod64(n_timestep):
+    """abar_0..abar_T in float64 from the float32 betas of schedule_tensors.  The float32 `alphas_cumprod` will not do for a jump
+    from t to s: 1 - abar_t / abar_s formed from it is wrong in its third digit at small t."""
+    return torch.cumprod(1.0 - cosine_betas(n_timestep).double(), 0)
+
+
+def _checked_steps(n_timestep, steps):
+    steps = [int(s) for s in steps]
+    if not steps or steps[0] > n_timestep or steps[-1] < 1 or any(a <= b for a, b in zip(steps, steps[1:])):
+        raise ValueError('steps must be strictly decreasing inside 1..%d, got %r' % (n_timestep, steps))
+    return steps
+
+
+def reverse_coefficients(n_timestep, steps, sampler='ancestral', eta=0.0):
+    """float64 [len(steps), 3] rows (A, Bz, C): iteration i denoises at t = steps[i] and lands on s = steps[i + 1] (s = 0 with
+    abar_0 = 1 after the last) by  x <- ((A x + Bz z) mask + scale C eps) mask.  The last iteration draws no noise; its C is
+    returned all the same.
+      'ancestral' (the variance choice of base.py:249-270 on the sub-sequence), a' = abar_t / abar_s, b' = 1 - a':
+          A = 1 / sqrt(a'),  Bz = -b' / (sqrt(1 - abar_t) sqrt(a')),  C = sqrt(b')
+      'ddim', sigma = eta sqrt((1 - abar_s) / (1 - abar_t)) sqrt(1 - abar_t / abar_s):
+          A = sqrt(abar_s / abar_t),  Bz = sqrt(max(0, 1 - abar_s - sigma^2)) - A sqrt(1 - abar_t),  C = sigma"""
+    if sampler not in SAMPLERS:
+        raise ValueError('sampler must be one of %s, got %r' % (', '.join(map(repr, SAMPLERS)), sampler))
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError('eta must be in [0, 1], got %r' % (eta,))
+    steps = _checked_steps(n_timestep, steps)
+    abar = alphas_cumprod64(n_timestep)
+    at, as_ = abar[steps], abar[steps[1:] + [0]]
+    if sampler == 'ancestral':
+        ap = at / as_
+        bp = 1.0 - ap
+        return torch.stack([1.0 / torch.sqrt(ap), -bp / (torch.sqrt(1.0 - at) * torch.sqrt(ap)), torch.sqrt(bp)], dim=1)
+    sigma = float(eta) * torch.sqrt((1.0 - as_) / (1.0 - at)) * torch.sqrt(1.0 - at / as_)
+    a = torch.sqrt(as_ / at)
+    return torch.stack([a, torch.sqrt(torch.clamp(1.0 - as_ - sigma ** 2, min=0.0)) - a * torch.sqrt(1.0 - at), sigma], dim=1)
+
+
+def twisted_coefficients(n_timestep, steps):
+    """float64 [len(steps), 3] rows (coef1, coef2, sigma) of the ancestral posterior on the sub-sequence, as the twisted sampler
+    uses them: mean = coef1 x0 + coef2 x_t with coef1 = sqrt(abar_s) b' / (1 - abar_t), coef2 = sqrt(a') (1 - abar_s) / (1 - abar_t),
+    and sigma = sqrt(b') (a', b', s as in reverse_coefficients)."""
+    steps = _checked_steps(n_timestep, steps)
+    abar = alphas_cumprod64(n_timestep)
+    at, as_ = abar[steps], abar[steps[1:] + [0]]
+    ap = at / as_
+    bp = 1.0 - ap
+    return torch.stack([torch.sqrt(as_) * bp / (1.0 - at), torch.sqrt(ap) * (1.0 - as_) / (1.0 - at), torch.sqrt(bp)], dim=1)
+
+
 def random_state_dict(dims, seed=0):
     """Random-init weights of the Denoiser architecture for benchmarking
     (trained checkpoints are not available offline).  Unlike the reference's

@@ -21,8 +21,10 @@ class ScaffoldRunner(MultiProcessor):
         return [{'motif_name': n} for n in names]
 
     def create_constants(self, params):
-        return {k: params[k] for k in ('rootdir', 'name', 'epoch', 'scale', 'strength', 'outdir', 'num_samples',
-                                       'batch_size', 'datadir')}
+        c = {k: params[k] for k in ('rootdir', 'name', 'epoch', 'scale', 'strength', 'outdir', 'num_samples',
+                                    'batch_size', 'datadir')}
+        c.update({k: params[k] for k in ('num_steps', 'sampler', 'eta') if params.get(k) is not None})      # few-step sampling, when asked for
+        return c
 
     def load_model(self, constants, device):
         return load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
@@ -37,7 +39,8 @@ class ScaffoldRunner(MultiProcessor):
                 sampler.sample({
                     'filepath': os.path.join(constants['datadir'], '{}.pdb'.format(task['motif_name'])),
                     'scale': constants['scale'], 'strength': constants['strength'], 'num_samples': batch,
-                    'outdir': outdir, 'prefix': task['motif_name'], 'offset': constants['num_samples'] - remaining})
+                    'outdir': outdir, 'prefix': task['motif_name'], 'offset': constants['num_samples'] - remaining,
+                    'num_steps': constants.get('num_steps'), 'sampler': constants.get('sampler'), 'eta': constants.get('eta')})
                 remaining -= batch
 
 
@@ -54,6 +57,12 @@ def build_parser():
     p.add_argument('--motif_name', type=str, help='Motif name', default=None)
     p.add_argument('--datadir', type=str, help='Data directory', default='data/design25')
     p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
+    p.add_argument('--num_steps', type=int, default=None,
+                   help='Run the reverse process on this many of the n_timestep steps; default: all (not in the reference CLI)')
+    p.add_argument('--sampler', type=str, choices=('ancestral', 'ddim'), default=None,
+                   help='Reverse step used with --num_steps; default: ancestral (not in the reference CLI)')
+    p.add_argument('--eta', type=float, default=None,
+                   help='DDIM noise level in [0, 1], 0 = deterministic; with --sampler ddim only (not in the reference CLI)')
     return p
 
 

@@ -18,7 +18,8 @@ class UnconditionalRunner(MultiProcessor):
                 for length in range(params['max_length'], params['min_length'] - 1, -params['length_step'])]
 
     def create_constants(self, params):
-        return {k: params.get(k) for k in ('rootdir', 'name', 'epoch', 'scale', 'outdir', 'num_samples', 'batch_size', 'resume')}
+        return {k: params.get(k) for k in ('rootdir', 'name', 'epoch', 'scale', 'outdir', 'num_samples', 'batch_size', 'resume',
+                                             'num_steps', 'sampler', 'eta')}
 
     def load_model(self, constants, device):
         return load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
@@ -38,7 +39,8 @@ class UnconditionalRunner(MultiProcessor):
                 sampler.sample({
                     'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': constants['outdir'], 'prefix': str(task['length']),
-                    'offset': constants['num_samples'] - remaining})
+                    'offset': constants['num_samples'] - remaining,
+                    'num_steps': constants.get('num_steps'), 'sampler': constants.get('sampler'), 'eta': constants.get('eta')})
                 remaining -= batch
 
 
@@ -57,6 +59,12 @@ def build_parser():
     p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
     p.add_argument('--sequential_order', action='store_true', help='Run in increasing order of length')
     p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist (not in the reference CLI)')
+    p.add_argument('--num_steps', type=int, default=None,
+                   help='Run the reverse process on this many of the n_timestep steps; default: all (not in the reference CLI)')
+    p.add_argument('--sampler', type=str, choices=('ancestral', 'ddim'), default=None,
+                   help='Reverse step used with --num_steps; default: ancestral (not in the reference CLI)')
+    p.add_argument('--eta', type=float, default=None,
+                   help='DDIM noise level in [0, 1], 0 = deterministic; with --sampler ddim only (not in the reference CLI)')
     return p
 
 

@@ -109,7 +109,8 @@ class MotifRunner(UnconditionalRunner):
                     'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
                     'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
-                    'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps']})
+                    'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
+                    'num_steps': constants.get('num_steps')})
                 if constants['write_motif_locations']:
                     write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
                 remaining -= batch
@@ -149,6 +150,9 @@ def build_parser():
     p.add_argument('--write_motif_locations', action='store_true',
                    help='Write outdir/motif_locations/{length}_{index}.txt: start and end residue of every motif segment in the '
                         'best-fitting placement (0-based, inclusive) and the superposed motif RMSD')
+    p.add_argument('--num_steps', type=int, default=None,
+                   help='Run the reverse process on this many of the n_timestep steps, with the ancestral kernel between them; default: all '
+                        '(an addition to the reference CLI, like --align)')
     return p
 
 

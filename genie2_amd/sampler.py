@@ -5,6 +5,11 @@
 (1 initial + one per step except the last, each [B,N,3] from the default
 generator of the model's device) -- but the loop body never returns to the
 host: all T steps are enqueued through `genie_sample_loop`.
+
+Optional params 'num_steps' = K, 'sampler' ('ancestral' | 'ddim') and 'eta'
+(DDIM only) run the reverse process on K of the T timesteps instead
+(pack.respaced_steps / reverse_coefficients, `genie_sample_loop_steps`); not in
+the reference.  Without them the path above is taken unchanged.
 """
 import os
 from abc import ABC, abstractmethod
@@ -12,6 +17,7 @@ from abc import ABC, abstractmethod
 import torch
 
 from . import features as F
+from . import pack
 
 
 class BaseSampler(ABC):
@@ -50,7 +56,25 @@ class BaseSampler(ABC):
         """The reference's draws (base.py:227,269), in its order, on its device."""
         return torch.stack([torch.randn(B, N, 3, device=self.device) for _ in range(T)])
 
+    def few_step_plan(self, params):
+        """None without 'num_steps' (the reference's T-step loop); else (steps, float64 coefficient rows) of the strided process.
+        Host only: every bad value raises ValueError here, before the device is touched."""
+        num_steps, sampler, eta = params.get('num_steps'), params.get('sampler'), params.get('eta')
+        if num_steps is None:
+            if sampler not in (None, 'ancestral') or eta is not None:
+                raise ValueError('sampler=%r / eta=%r need num_steps' % (sampler, eta))
+            return None
+        T = self.model.config.diffusion['n_timestep']
+        sampler = 'ancestral' if sampler is None else sampler
+        eta = pack.check_sampler(sampler, eta)
+        steps = pack.respaced_steps(T, num_steps)
+        noise = params.get('noise')
+        if noise is not None and (noise.dim() != 4 or noise.shape[0] != len(steps)):
+            raise ValueError('noise must be [%d, B, N, 3] with num_steps=%d, got %s' % (len(steps), len(steps), tuple(noise.shape)))
+        return steps, pack.reverse_coefficients(T, steps, sampler, eta)
+
     def _sample(self, params):
+        plan = self.few_step_plan(params)
         feats = F.convert_np_features_to_tensor(
             F.batchify_np_features([self.create_np_features(params) for _ in range(params['num_samples'])]),
             self.device)
@@ -58,10 +82,13 @@ class BaseSampler(ABC):
         T = self.model.config.diffusion['n_timestep']
         noise = params.get('noise')
         if noise is None:
-            noise = self.draw_noise(B, N, T)
+            noise = self.draw_noise(B, N, T if plan is None else len(plan[0]))
         denoiser = self.model.model
         eng = denoiser.bind(feats)
-        trans, _, _ = eng.sample_loop(noise, params['scale'], quat_codes=params.get('quat_codes'))
+        if plan is None:
+            trans, _, _ = eng.sample_loop(noise, params['scale'], quat_codes=params.get('quat_codes'))
+        else:
+            trans, _, _ = eng.sample_loop_steps(noise, params['scale'], plan[0], plan[1], quat_codes=params.get('quat_codes'))
         feats['atom_positions'] = trans.detach().cpu()
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 

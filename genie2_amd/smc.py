@@ -123,6 +123,10 @@ class TwistedSampler(UnconditionalSampler):
     After _sample, `last_fit` holds what the twisting function's `locate` says of the final coordinates (MotifPotential.locate: 'best',
     'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample; with motif groups also 'group_rmsd' and the 'groups' labels),
     or None when it has no `locate`.
+    Optional 'num_steps' = K (not in the reference) visits the K timesteps of pack.respaced_steps with the ancestral kernel between
+    them (pack.twisted_coefficients): `ess_trace` then has K - 1 entries, the last visited step takes the role of step 1, and
+    `last_unguided_steps` and the potential keep reading the timestep itself.  'sampler': 'ddim' is refused (ValueError): the
+    weights are ratios of the Gaussian transition densities of the ancestral kernel.
     A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it."""
 
     def __init__(self, model):
@@ -130,12 +134,22 @@ class TwistedSampler(UnconditionalSampler):
             raise NotImplementedError('triangular attention: sampling only (the twisted sampler needs the denoiser VJP through it)')
         super().__init__(model)
 
+    def few_step_plan(self, params):
+        if params.get('sampler') not in (None, 'ancestral'):
+            pack.check_sampler(params['sampler'])                       # (an unknown name is its own error)
+            raise ValueError('the twisted sampler has the ancestral kernel only, got sampler=%r' % (params['sampler'],))
+        plan = super().few_step_plan(params)
+        return None if plan is None else (plan[0], pack.twisted_coefficients(self.model.config.diffusion['n_timestep'], plan[0]))
+
     def _sample(self, params):
+        plan = self.few_step_plan(params)
         feats = F.convert_np_features_to_tensor(
             F.batchify_np_features([self.create_np_features(params) for _ in range(params['num_samples'])]), self.device)
         B, N = feats['residue_mask'].shape
         m = self.model
         T = m.config.diffusion['n_timestep']
+        steps = list(range(T, 0, -1)) if plan is None else plan[0]
+        tw_coef = None if plan is None else plan[1].to(device=self.device, dtype=torch.float32)
         sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(T).items()}
         abar, betas = sched['alphas_cumprod'], sched['betas']
         noise = params.get('noise')
@@ -158,7 +172,7 @@ class TwistedSampler(UnconditionalSampler):
         rots = eng.frenet(trans)
         self.ess_trace, self.resampled_at = [], []
         us = list(params.get('resample_u', []))
-        for it, step in enumerate(range(T, 0, -1)):
+        for it, step in enumerate(steps):
             ts = torch.full((B,), step, dtype=torch.int32, device=self.device)
             c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
             z = eng.denoise(trans, rots, ts)['z']
@@ -172,13 +186,16 @@ class TwistedSampler(UnconditionalSampler):
             grad = grad * alpha * norm / (alpha + norm)                           # (:483-488)
             x0u = x0.detach()
             x0t = x0u + grad if step >= int(params.get('last_unguided_steps', 50)) else x0u
-            coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
-            coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
+            if tw_coef is None:
+                coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
+                coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
+                sigma = sched['sqrt_betas'][step]
+            else:           # the same posterior between step and the next visited one (float64 on the host, pack.twisted_coefficients)
+                coef1, coef2, sigma = tw_coef[it]
             mean_t, mean_u = coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans
-            if step == 1:
+            if it == len(steps) - 1:
                 trans = mean_t
                 break
-            sigma = sched['sqrt_betas'][step]
             new = (mean_t + params['scale'] * sigma * draw(it + 1)) * mask
             log_rev = log_normal_density(new, mean_u, sigma ** 2).sum(dim=(1, 2))
             log_tw = log_normal_density(new, mean_t, sigma ** 2).sum(dim=(1, 2))

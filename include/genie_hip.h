@@ -236,6 +236,28 @@ int genie_sample_loop(genie_handle_t h, genie_stream_t stream, float scale,
                       int first_step, int last_step,
                       float* trans_io, float* rots_io, float* record);
 
+/* genie_p_sample in coefficient form, for a step from timestep t to any s < t and for either sampler:
+ * trans <- ((a trans + bz z) * mask [+ c_scaled eps]) * mask, then Frenet frames.  eps == NULL: no noise (the last step).
+ * genie_p_sample(step, scale) is a = 1/sqrt(alpha_t), bz = -w_z/sqrt(alpha_t), c_scaled = scale sqrt(beta_t); the rows of
+ * pack.reverse_coefficients give (a, bz, C) for strided ancestral and DDIM steps, c_scaled = scale * C.
+ * Returns GENIE_E_ARG, before anything is launched, for a NULL trans_inout, rots_out or z and for a non-finite coefficient. */
+int genie_reverse_step(genie_handle_t h, genie_stream_t stream, float a, float bz, float c_scaled,
+                       float* trans_inout, float* rots_out, const float* z, const float* eps /* NULL: no noise */);
+
+/* genie_sample_loop over a sub-sequence of the timesteps, device resident (no host read): iteration i denoises at steps[i] and
+ * applies genie_reverse_step with coef[i]; the last iteration draws no noise.  With start_from_noise the state starts as noise[0]
+ * and its frames; without, trans_io / rots_io carry it in and noise[0] is not read (a resumed loop passes the tail of steps, coef,
+ * noise and quat_codes, beginning one before the first remaining draw).
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error naming this entry: n_iter < 1; steps not strictly
+ * decreasing or outside 1..n_timestep; NULL steps, coef, trans_io or rots_io; NULL noise when start_from_noise or n_iter > 1;
+ * a non-finite coefficient. */
+int genie_sample_loop_steps(genie_handle_t h, genie_stream_t stream, int n_iter,
+                            const int32_t* steps /*host, strictly decreasing, in 1..T*/,
+                            const float* coef /*host [n_iter][3]: a, bz, c_scaled*/,
+                            const float* noise /*[n_iter][B,N,3]: noise[0] initial trans when start_from_noise, noise[k] the draw of iteration k-1's landing*/,
+                            const int8_t* quat_codes /*NULL or [n_iter][B,N,N]*/, int start_from_noise,
+                            float* trans_io, float* rots_io, float* record /*NULL or [n_iter][B,N,3]*/);
+
 /* ---- arithmetic -------------------------------------------------------- */
 
 /* How the pair-stack GEMMs (triangle multiplication, pair transition: 95 % of the FLOPs of
