@@ -106,6 +106,9 @@ SYMBOLS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     'genie_motif_potential_grouped_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'genie_smc_reweight': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double] + [C.c_void_p] * 7 +
+                           [C.c_size_t]),
+    'genie_smc_reweight_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h

@@ -20,6 +20,9 @@ size_t ipa_attn_lds(const genie_dims_t& d, int N);
 
 static char g_create_err[512] = "";
 
+// what genie_last_error(NULL) returns, for the entries that take no handle (smc_step_kernels.hip)
+void set_handle_free_error(const char* msg) { snprintf(g_create_err, sizeof g_create_err, "%s", msg); }
+
 #define SET_ERR(h, ...) do { snprintf((h)->err, sizeof((h)->err), __VA_ARGS__); } while (0)
 #define HIP_TRY(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     SET_ERR(h, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return GENIE_E_HIP; } } while (0)

@@ -15,7 +15,11 @@ the sample best after optimal superposition, then a last line `# rmsd <motif RMS
 `--motif_groups file` reads the motif group of every segment from the problem file (column 29 of REMARK 999 INPUT, as the scaffold
 CLI does): segments of one group keep their relative pose, different groups are guided as independent bodies, and the location files
 end with one more line per group, `# rmsd group <label> <that group's own RMSD>`.  The default, `joint`, treats all segments as one
-rigid motif."""
+rigid motif.
+
+`--num_particles K` makes every design a particle system of its own: `--num_samples` then counts designs, `--batch_size` designs per
+sampler call (a device batch of batch_size * K particles), and each system's best particle (the largest accumulated weight) is the
+one written, one PDB and one location file per design.  Without it a batch is one system and every particle is written."""
 import argparse
 import os
 
@@ -83,6 +87,7 @@ class MotifRunner(UnconditionalRunner):
         c['segments'] = load_motif_segments(params['motif_file'])
         c['motif_groups'] = params.get('motif_groups', 'joint')
         c['groups'] = load_motif_groups(params['motif_file']) if c['motif_groups'] == 'file' else None
+        c['num_particles'] = params.get('num_particles')
         return c
 
     def execute(self, constants, tasks, device):
@@ -105,12 +110,15 @@ class MotifRunner(UnconditionalRunner):
                 potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
                                            max_offsets=constants['max_offsets'], device=device, align=constants['align'],
                                            groups=constants.get('groups'))
+                # (with --num_particles: `batch` systems, each returning its best particle)
+                systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'],
+                                                                             'return_particles': 'best'}
                 sampler.sample({
                     'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
                     'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
-                    'num_steps': constants.get('num_steps')})
+                    'num_steps': constants.get('num_steps'), **systems})
                 if constants['write_motif_locations']:
                     write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
                 remaining -= batch
@@ -153,6 +161,10 @@ def build_parser():
     p.add_argument('--num_steps', type=int, default=None,
                    help='Run the reverse process on this many of the n_timestep steps, with the ancestral kernel between them; default: all '
                         '(an addition to the reference CLI, like --align)')
+    p.add_argument('--num_particles', type=int, default=None,
+                   help='Guide every design as a particle system of its own with this many particles (1..64) and write its best '
+                        'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
+                        'written (an addition to the reference CLI, like --align)')
     return p
 
 

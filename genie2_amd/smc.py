@@ -8,6 +8,8 @@ MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
 potential reproduces the ancestral sampler, (c) that the guided gradient equals torch autograd through the oracle."""
+import numbers
+
 import torch
 
 from . import features as F
@@ -127,7 +129,16 @@ class TwistedSampler(UnconditionalSampler):
     them (pack.twisted_coefficients): `ess_trace` then has K - 1 entries, the last visited step takes the role of step 1, and
     `last_unguided_steps` and the potential keep reading the timestep itself.  'sampler': 'ddim' is refused (ValueError): the
     weights are ratios of the Gaussian transition densities of the ancestral kernel.
-    A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it."""
+    A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it.
+
+    Optional 'num_particles' = K in 1..64 (not in the reference; the fork's latest sampler has the layout) makes 'num_samples' = S
+    independent particle systems of K particles each in one device batch of S K, system-major (particle b belongs to system b // K):
+    weights, ESS, resampling and the gradient-norm cap are per system, and the SMC bookkeeping of a step is one genie_smc_reweight
+    call (csrc/smc_step_kernels.hip) with no host read inside the loop.  'noise' is then [T, S K, N, 3]; entry `it` of 'resample_u'
+    is a scalar for every system or S values; `ess_trace` is a CPU tensor [steps - 1, S], `resampled_at` a list of S lists of steps,
+    `last_log_weights` [S, K] the accumulated log-weights after the last weight update and `last_choice` [S] their argmax (the lowest
+    index of equal ones).  'return_particles': 'all' (default) returns the S K structures, 'best' particle last_choice[s] of every
+    system (S structures, `last_fit` with S rows).  Without 'num_particles' nothing of this applies: one system of num_samples."""
 
     def __init__(self, model):
         if getattr(model.model, 'dims', {}).get('n_head_tri', 0):       # before any device work
@@ -142,6 +153,8 @@ class TwistedSampler(UnconditionalSampler):
         return None if plan is None else (plan[0], pack.twisted_coefficients(self.model.config.diffusion['n_timestep'], plan[0]))
 
     def _sample(self, params):
+        if params.get('num_particles') is not None or params.get('return_particles') is not None:
+            return self._sample_systems(params)
         plan = self.few_step_plan(params)
         feats = F.convert_np_features_to_tensor(
             F.batchify_np_features([self.create_np_features(params) for _ in range(params['num_samples'])]), self.device)
@@ -218,6 +231,167 @@ class TwistedSampler(UnconditionalSampler):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans.detach()).items()}
         feats['atom_positions'] = trans.detach().cpu()
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
+
+    def _sample_systems(self, params):
+        """_sample for params['num_particles'] = K: S = num_samples independent systems of K particles (the class docstring).  The
+        loop body is _sample's, with the norm cap per system and lines "new = ..." to "trans = new" as one genie_smc_reweight call."""
+        K, S, keep = params.get('num_particles'), params['num_samples'], params.get('return_particles', 'all')
+        if K is None:
+            raise ValueError("return_particles=%r needs num_particles" % (keep,))
+        if isinstance(K, bool) or not isinstance(K, numbers.Integral) or not 1 <= K <= SMC_MAX_PARTICLES:
+            raise ValueError('num_particles must be an integer in 1..%d, got %r' % (SMC_MAX_PARTICLES, K))
+        if keep not in ('all', 'best'):
+            raise ValueError("return_particles must be 'all' or 'best', got %r" % (keep,))
+        K = int(K)
+        plan = self.few_step_plan(params)
+        m = self.model
+        T = m.config.diffusion['n_timestep']
+        steps = list(range(T, 0, -1)) if plan is None else plan[0]
+        noise = params.get('noise')
+        if noise is not None and (noise.dim() != 4 or noise.shape[0] != len(steps) or noise.shape[1] != S * K):
+            raise ValueError('noise must be [%d, %d, N, 3] with num_samples=%d and num_particles=%d, got %s'
+                             % (len(steps), S * K, S, K, tuple(noise.shape)))
+        us = list(params.get('resample_u', []))
+        us = [[float(e)] * S if _is_scalar(e) else [float(v) for v in e] for e in us]
+        if any(len(e) != S for e in us):
+            raise ValueError('an entry of resample_u is a scalar or %d values, one per system' % S)
+        feats = F.convert_np_features_to_tensor(
+            F.batchify_np_features([self.create_np_features(params) for _ in range(S * K)]), self.device)
+        B, N = feats['residue_mask'].shape
+        tw_coef = None if plan is None else plan[1].to(device=self.device, dtype=torch.float32)
+        sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(T).items()}
+        abar, betas = sched['alphas_cumprod'], sched['betas']
+        draw = (lambda k: noise[k].to(self.device)) if noise is not None else (lambda k: torch.randn(B, N, 3, device=self.device))
+        twist = params.get('twisting_function')
+        if twist is None:
+            segs = [torch.as_tensor(x, dtype=torch.float32) for x in params['motif_target']]
+            pm = placement_masks(generate_motif_index_mask(segs, N)).to(self.device)
+            tgt = torch.cat(segs).to(self.device)
+            tgt = tgt - tgt.mean(dim=0, keepdim=True)
+            tausq = float(params.get('tausq', 0.012))
+            twist = lambda x0, step: motif_twisting_function(x0, pm, tgt, abar[step], tausq)      # noqa: E731
+        alpha = float(params.get('guidance_alpha', 0.012))
+        ess_fraction = float(params.get('ess_threshold', 0.5))
+        eng = m.model.bind(feats)
+        w = pack.flatten_state_dict(m.model.state_dict(), m.model.dims).to(self.device)
+        mask = feats['residue_mask'].unsqueeze(-1).float()
+        trans = draw(0)
+        log_proposal = log_normal_density(trans, torch.tensor(0., device=self.device), torch.tensor(1., device=self.device)).sum(dim=(1, 2))
+        log_w_acc = torch.zeros(B, device=self.device)
+        rots = eng.frenet(trans)
+        reweight = SmcReweight(S, K, N, self.device)
+        ess_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.float32, device=self.device)
+        resampled_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.int32, device=self.device)
+        for it, step in enumerate(steps):
+            ts = torch.full((B,), step, dtype=torch.int32, device=self.device)
+            c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
+            z = eng.denoise(trans, rots, ts)['z']
+            x0 = ((trans - c1 * z) / c0).detach().requires_grad_(True)
+            log_prob = twist(x0, step)
+            g = torch.autograd.grad(log_prob.mean(), x0)[0] * B
+            _, dz_part = eng.denoise_vjp(w, trans, rots, ts, (-c1 / c0) * g)
+            grad = g / c0 + dz_part
+            # the cap of (:483-488) over a system's own K particles: a system's step must not depend on its batch neighbours
+            norm = grad.double().view(S, -1).norm(dim=1).float().view(S, 1, 1, 1)
+            grad = (grad.view(S, K, N, 3) * alpha * norm / (alpha + norm)).view(B, N, 3)
+            x0u = x0.detach()
+            x0t = x0u + grad if step >= int(params.get('last_unguided_steps', 50)) else x0u
+            if tw_coef is None:
+                coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
+                coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
+                sigma = sched['sqrt_betas'][step]
+            else:
+                coef1, coef2, sigma = tw_coef[it]
+            mean_t, mean_u = coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans
+            if it == len(steps) - 1:
+                trans = mean_t
+                break
+            new = (mean_t + params['scale'] * sigma * draw(it + 1)) * mask
+            if it < len(us):
+                u = torch.tensor(us[it], dtype=torch.float32).to(self.device)
+            else:
+                u = torch.rand(S, device=self.device) / K
+            trans, _ = reweight(new, mean_t, mean_u, sigma, log_prob.detach(), u, ess_fraction, log_proposal, log_w_acc,
+                                ess_out=ess_dev[it], resampled_out=resampled_dev[it])
+            rots = eng.frenet(trans)
+        # the one host read of the run
+        self.ess_trace = ess_dev.cpu()
+        flags = resampled_dev.cpu()
+        self.resampled_at = [[steps[it] for it in range(flags.shape[0]) if int(flags[it, s])] for s in range(S)]
+        self.last_log_weights = log_w_acc.detach().cpu().view(S, K)
+        top = self.last_log_weights == self.last_log_weights.max(dim=1, keepdim=True).values
+        first = torch.where(top, torch.arange(K).expand(S, K), torch.full((S, K), K)).min(dim=1).values
+        self.last_choice = torch.where(first < K, first, torch.zeros_like(first))       # (no entry equals a NaN max: particle 0)
+        trans = trans.detach()
+        if keep == 'best':
+            pick = (torch.arange(S) * K + self.last_choice).to(self.device)
+            trans = trans[pick]
+            feats = {k: (v[pick] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for k, v in feats.items()}
+        self.last_fit = None
+        if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
+            self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans).items()}
+        feats['atom_positions'] = trans.cpu()
+        return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
+
+
+SMC_MAX_PARTICLES = 64          # K of genie_smc_reweight: one wave holds a system
+
+
+def _is_scalar(x):
+    return isinstance(x, numbers.Real) or (torch.is_tensor(x) and x.dim() == 0)
+
+
+class SmcReweight:
+    """genie_smc_reweight (include/genie_hip.h) for S systems of K particles of N residues on `device`: one call does, per system,
+    what smc.py's loop does after the draw -- the weight update, the ESS, systematic resampling below `ess_fraction` K or the
+    renormalisation above it -- on torch's current stream, without a host read.  `log_proposal` and `log_w_acc` [S K] are updated in
+    place; returns (x_out [S K, N, 3], index [S K] int32: every particle's ancestor as a batch index) and leaves the ESS and the 0 / 1
+    resampling flag of every system in `ess_out` / `resampled_out` [S] (its own `ess`, `resampled` when none are given)."""
+
+    def __init__(self, S, K, N, device='cuda'):
+        from . import capi
+        self.lib = capi.load_library()
+        self.S, self.K, self.N = int(S), int(K), int(N)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise capi.GenieError('genie_smc_reweight runs on the GPU (libgenie_hip); there is no CPU path')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        need = self.lib.genie_smc_reweight_work_bytes(self.S, self.K, self.N)
+        if need == 0:
+            raise ValueError('S = %d, K = %d, N = %d: needs S, N >= 1 and K in 1..%d' % (self.S, self.K, self.N, SMC_MAX_PARTICLES))
+        self.work = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+        self.ess = torch.zeros(self.S, dtype=torch.float32, device=self.device)
+        self.resampled = torch.zeros(self.S, dtype=torch.int32, device=self.device)
+
+    def __call__(self, x_new, mean_tw, mean_un, sigma, log_prob, u, ess_fraction, log_proposal, log_w_acc, ess_out=None,
+                 resampled_out=None, x_out=None, work_bytes=None):
+        import ctypes as C
+        B, f32 = self.S * self.K, torch.float32
+        ess_out = self.ess if ess_out is None else ess_out
+        resampled_out = self.resampled if resampled_out is None else resampled_out
+        ins = [t.detach().to(f32).contiguous() for t in (x_new, mean_tw, mean_un)]
+        sigma = sigma.detach().to(f32).reshape(1).contiguous()
+        log_prob, u = log_prob.detach().to(f32).contiguous(), u.detach().to(f32).contiguous()
+        for t, shape, dtype in ((ins[0], (B, self.N, 3), f32), (ins[1], (B, self.N, 3), f32), (ins[2], (B, self.N, 3), f32),
+                                (log_prob, (B,), f32), (u, (self.S,), f32), (log_proposal, (B,), f32), (log_w_acc, (B,), f32),
+                                (ess_out, (self.S,), f32), (resampled_out, (self.S,), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError('genie_smc_reweight: expected a contiguous %s %s on %s, got %s %s on %s'
+                                 % (dtype, shape, self.device, t.dtype, tuple(t.shape), t.device))
+        x_out = torch.empty_like(ins[0]) if x_out is None else x_out
+        index = torch.empty(B, dtype=torch.int32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+        with torch.cuda.device(self.device):
+            rc = self.lib.genie_smc_reweight(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), self.S, self.K, self.N,
+                                             p(ins[0]), p(ins[1]), p(ins[2]), p(sigma), p(log_prob), p(u), float(ess_fraction),
+                                             p(log_proposal), p(log_w_acc), p(x_out), p(index), p(ess_out), p(resampled_out),
+                                             p(self.work), self.work.numel() * 8 if work_bytes is None else work_bytes)
+        if rc != 0:
+            from . import capi
+            msg = self.lib.genie_last_error(None)
+            raise capi.GenieError('genie_smc_reweight failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        return x_out, index
 
 
 def placement_starts(locs):

@@ -97,7 +97,7 @@ typedef struct {
  * touched; genie_last_error(NULL) names the field. */
 int genie_create(const genie_dims_t* dims, int device, genie_handle_t* out);
 void genie_destroy(genie_handle_t h);
-const char* genie_last_error(genie_handle_t h);   /* h may be NULL: last create error */
+const char* genie_last_error(genie_handle_t h);   /* h may be NULL: last error of genie_create or of an entry that takes no handle */
 
 /* Number of fp32 values genie_load_weights expects for these dims. */
 size_t genie_weight_count(const genie_dims_t* dims);
@@ -206,6 +206,36 @@ int genie_motif_potential_grouped(genie_stream_t stream, int B, int N, const flo
                                   float* rmsd_out /*[B] or NULL*/, float* group_rmsd_out /*[B,G] or NULL*/, void* work,
                                   size_t work_bytes);
 size_t genie_motif_potential_grouped_work_bytes(int B, int P, int G, int align);
+
+/* The SMC bookkeeping of one twisted step for S independent particle systems of K particles each, without a handle: the fork's weight
+ * helpers, systematic resampling and the weight update of its loop (genie/sampler/unconditional_smc.py:25-43, 237-288, 540-576;
+ * genie2_amd/smc.py:212-226 restates them in PyTorch for one system).  Layout is system-major: particle b belongs to system b / K.
+ * For every system s on its own, over its K particles:
+ *   d_b     = sum_{n,c} [ (x_new - mean_tw)^2 - (x_new - mean_un)^2 ] / (2 sigma^2)   (= log_rev - log_tw: the log sigma terms cancel)
+ *   log_w_b = d_b + log_prob_b - log_proposal_b + log_w_acc_b
+ *   ess_s   = (sum w)^2 / sum w^2,  w = softmax of log_w over the system
+ *   if ess_s < ess_fraction K:  systematic resampling with the points u_s + i / K, i = 0..K-1: the ancestor of particle i is the
+ *       number of cumulative sums of w strictly below its point, clamped into the system;
+ *       x_out[b] = x_new[ancestor],  log_proposal[b] = log_prob[ancestor],  log_w_acc[b] = 0
+ *   else:  x_out = x_new,  log_proposal = log_prob,  log_w_acc = log_w - logsumexp_s(log_w) + log K
+ * All N rows are summed (the twisted sampler's batches are never ragged).  index_out[b] is the ancestor as a batch index (b itself
+ * where the system did not resample), ess_out[s] the effective sample size, resampled_out[s] 1 or 0.  A particle whose log_w is -inf
+ * has weight exactly 0 and is never an ancestor (the clamp is to the first and last particle of non-zero weight).  A system whose
+ * largest log_w is not finite (a NaN counts) is left in place: identity indices, resampled_out 0, log_w_acc as the formula gives it.
+ * Two launches on `stream`: the first sums d_b, one work-group per particle, and writes log_w_b to `work` (a double per particle:
+ * genie_smc_reweight_work_bytes(S, K, N) bytes, 8-byte aligned); the second copies x_out, every work-group redoing its system's
+ * K-value tail in one wave.  The sums of d_b and the whole tail (softmax, ESS, cumulative sums, the comparison with the points) run
+ * in float64, in a fixed order, without atomics: two calls on the same inputs give bitwise the same outputs.  No allocation, no
+ * synchronisation, no host read.
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error(NULL) naming this entry: a NULL pointer; K outside 1..64;
+ * S < 1; N < 1; x_out overlapping x_new; log_proposal overlapping log_prob; a non-finite ess_fraction; work_bytes below
+ * genie_smc_reweight_work_bytes(S, K, N). */
+int genie_smc_reweight(genie_stream_t stream, int S, int K, int N, const float* x_new /*[S K,N,3]*/, const float* mean_tw /*[S K,N,3]*/,
+                       const float* mean_un /*[S K,N,3]*/, const float* sigma /*[1], device*/, const float* log_prob /*[S K]*/,
+                       const float* u /*[S], each in [0, 1/K)*/, double ess_fraction, float* log_proposal /*[S K], in/out*/,
+                       float* log_w_acc /*[S K], in/out*/, float* x_out /*[S K,N,3]*/, int32_t* index_out /*[S K]*/,
+                       float* ess_out /*[S]*/, int32_t* resampled_out /*[S]*/, void* work, size_t work_bytes);
+size_t genie_smc_reweight_work_bytes(int S, int K, int N);
 
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
