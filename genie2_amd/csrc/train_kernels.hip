@@ -524,6 +524,8 @@ static void launch_gemm_t(hipStream_t st, const GemmP& p, dim3 grid, bool akc, b
 }
 // terms: bf16 pieces per operand -- 1: plain bf16 (one MFMA per product), 2: 16 significand bits (three MFMAs), 3: 24 bits (six)
 // which kernel launch_gemm runs a product on: 2 the 128-tile kernel, 1 the 64-tile kernel, 0 the generic one
+// (tests/_train_paths.py replays this function and gemm_splits below in Python to state which shapes reach which kernel: the two
+//  sides move together)
 static int gemm_kernel_choice(const GemmP& p) {
     const bool ua = p.ak == 1 || p.am == 1, ub = p.bk == 1 || p.bn == 1;
     const long long ks = ((p.K + p.nsplit - 1) / p.nsplit + GM_BK - 1) / GM_BK * GM_BK;
@@ -597,6 +599,7 @@ void launch_gemm(hipStream_t st, const GemmP& p_in, int terms) {
 }
 // split-K factor for a reduction of length K into `tiles` output tiles (x batch): enough work-groups to fill the chip, at least 128 of
 // K each.  Only for mode 2 (atomic accumulation).
+// (replayed in tests/_train_paths.py, like gemm_kernel_choice above: the two sides move together)
 #define GM_SPLIT_WGS 512      // work-groups of a multi-tile split-K GEMM: two per CU, so that one's operand staging runs under the other's MFMAs
 int gemm_splits(long long M, long long N, long long K, long long batch) {
     // several 128 x 128 output tiles: one work-group of the 128-tile kernel per CU (its LDS admits one) -- the 64-tile kernel spends
@@ -926,38 +929,45 @@ void launch_pair_features(hipStream_t st, const float* trans, const float* rots,
 // gradient of the template distance bins wrt the (scaled) translations: F_k = pm softmax_k(-4 |d - v_k|), d = sqrt(1e-10 + |x_i - x_j|^2)
 // (pair_feature_net.py:223-269, geo_utils.py:4-19).  dF: [P][ldf], the first nbin columns.  The quaternion features depend on the
 // frames only, which the guidance samplers detach (unconditional_smc.py:466, 570-576).
-__global__ __launch_bounds__(256) void k_pair_features_bwd(const float* __restrict__ dF, int ldf, const float* __restrict__ trans,
-                                                           const float* __restrict__ rmask, float* __restrict__ dtr, int B, int N, int nbin,
-                                                           float dmin, float dstep) {
-    const long long pidx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (pidx >= (long long)B * N * N) return;
-    const int j = (int)(pidx % N), i = (int)((pidx / N) % N), b = (int)(pidx / ((long long)N * N));
-    const float pm = rmask[b * N + i] * rmask[b * N + j];
-    if (pm == 0.f || i == j) return;
-    const float* xi = trans + (size_t)(b * N + i) * 3;
-    const float* xj = trans + (size_t)(b * N + j) * 3;
-    const float dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
-    const float d = sqrtf(1e-10f + dx * dx + dy * dy + dz * dz);
-    float mx = -3.0e38f;
-    for (int k = 0; k < nbin; ++k) mx = fmaxf(mx, -4.0f * fabsf(d - (dmin + (float)k * dstep)));
-    float s = 0.f, sg = 0.f, sfg = 0.f, sf = 0.f;
-    const float* g = dF + pidx * ldf;
-    for (int k = 0; k < nbin; ++k) {
-        const float v = dmin + (float)k * dstep;
-        const float e = expf(-4.0f * fabsf(d - v) - mx);
-        const float dl = d > v ? -4.0f : (d < v ? 4.0f : 0.f);      // d logit_k / d d
-        s += e; sg += e * dl; sfg += e * g[k] * dl; sf += e * g[k];
+__global__ __launch_bounds__(64) void k_pair_features_bwd(const float* __restrict__ dF, int ldf, const float* __restrict__ trans,
+                                                          const float* __restrict__ rmask, float* __restrict__ dtr, int B, int N, int nbin,
+                                                          float dmin, float dstep) {
+    // One wave per residue (b, i): x_i enters the pairs (i, j) and (j, i), whose bins share the distance, so lane j takes both rows of dF
+    // at once and the wave sums its lanes in a fixed order -- no float atomics: the guidance samplers amplify a rounding-level difference
+    // of this gradient over their steps, and two runs of one sampler have to agree.
+    const int bi = blockIdx.x, b = bi / N, i = bi - b * N, lane = threadIdx.x;
+    const float mi = rmask[bi];
+    const float* xi = trans + (size_t)bi * 3;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int j = lane; j < N && mi != 0.f; j += 64) {
+        const float pm = mi * rmask[b * N + j];
+        if (pm == 0.f || i == j) continue;
+        const float* xj = trans + (size_t)(b * N + j) * 3;
+        const float dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
+        const float d = sqrtf(1e-10f + dx * dx + dy * dy + dz * dz);
+        float mx = -3.0e38f;
+        for (int k = 0; k < nbin; ++k) mx = fmaxf(mx, -4.0f * fabsf(d - (dmin + (float)k * dstep)));
+        float s = 0.f, sg = 0.f, sfg = 0.f, sf = 0.f;
+        const float* g1 = dF + ((long long)bi * N + j) * ldf;                   // pair (i, j)
+        const float* g2 = dF + (((long long)b * N + j) * N + i) * ldf;          // pair (j, i)
+        for (int k = 0; k < nbin; ++k) {
+            const float v = dmin + (float)k * dstep;
+            const float e = expf(-4.0f * fabsf(d - v) - mx);
+            const float dl = d > v ? -4.0f : (d < v ? 4.0f : 0.f);      // d logit_k / d d
+            const float g = g1[k] + g2[k];
+            s += e; sg += e * dl; sfg += e * g * dl; sf += e * g;
+        }
+        // y_k = e_k / s;  dL/dd = pm sum_k g_k y_k (dl_k - sum_m y_m dl_m)
+        const float c = pm * (sfg / s - (sf / s) * (sg / s)) / d;
+        ax += c * dx; ay += c * dy; az += c * dz;
     }
-    // y_k = e_k / s;  dL/dd = pm sum_k g_k y_k (dl_k - sum_m y_m dl_m)
-    const float dd = pm * (sfg / s - (sf / s) * (sg / s));
-    const float c = dd / d;
-    atomicAdd(dtr + (size_t)(b * N + i) * 3, c * dx); atomicAdd(dtr + (size_t)(b * N + i) * 3 + 1, c * dy); atomicAdd(dtr + (size_t)(b * N + i) * 3 + 2, c * dz);
-    atomicAdd(dtr + (size_t)(b * N + j) * 3, -c * dx); atomicAdd(dtr + (size_t)(b * N + j) * 3 + 1, -c * dy); atomicAdd(dtr + (size_t)(b * N + j) * 3 + 2, -c * dz);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o); }
+    if (lane == 0) { dtr[(size_t)bi * 3] = ax; dtr[(size_t)bi * 3 + 1] = ay; dtr[(size_t)bi * 3 + 2] = az; }
 }
 void launch_pair_features_bwd(hipStream_t st, const float* dF, int ldf, const float* trans, const float* rmask, float* dtr, int B, int N, int nbin,
                               float dmin, float dstep) {
-    const long long P = (long long)B * N * N;
-    hipLaunchKernelGGL(k_pair_features_bwd, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, dF, ldf, trans, rmask, dtr, B, N, nbin, dmin, dstep);
+    hipLaunchKernelGGL(k_pair_features_bwd, dim3((unsigned)(B * N)), dim3(64), 0, st, dF, ldf, trans, rmask, dtr, B, N, nbin, dmin, dstep);
 }
 
 // p[b,i,j,:] = (p[b,i,j,:] + pi[b,i,:] + pj[b,j,:]) * mask   and its transpose: dpi[b,i,:] = sum_j dp, dpj[b,j,:] = sum_i dp
@@ -1141,14 +1151,16 @@ __global__ __launch_bounds__(IPA_NT) void k_ipa_bwd_q(IpaDims d, const float* __
         doptg[((size_t)bi * H * Pv + u) * 3] = w0; doptg[((size_t)bi * H * Pv + u) * 3 + 1] = w1; doptg[((size_t)bi * H * Pv + u) * 3 + 2] = w2;
         // dR[a][c] += w_a dl_c with w = R l;  dt -= d w
         const float x0 = R[0] * l0 + R[1] * l1 + R[2] * l2, x1 = R[3] * l0 + R[4] * l1 + R[5] * l2, x2 = R[6] * l0 + R[7] * l1 + R[8] * l2;
-        atomicAdd(red + 0, x0 * g0); atomicAdd(red + 1, x0 * g1); atomicAdd(red + 2, x0 * g2);
-        atomicAdd(red + 3, x1 * g0); atomicAdd(red + 4, x1 * g1); atomicAdd(red + 5, x1 * g2);
-        atomicAdd(red + 6, x2 * g0); atomicAdd(red + 7, x2 * g1); atomicAdd(red + 8, x2 * g2);
-        atomicAdd(red + 9, -w0); atomicAdd(red + 10, -w1); atomicAdd(red + 11, -w2);
+        float* xg = red + 16 + u * 6;           // (the pair-row tile's space, not in use yet)
+        xg[0] = x0; xg[1] = x1; xg[2] = x2; xg[3] = g0; xg[4] = g1; xg[5] = g2;
     }
     __syncthreads();
-    if (tid < 9) dR[(size_t)bi * 9 + tid] += red[tid];
-    else if (tid < 12) dT[(size_t)bi * 3 + tid - 9] += red[tid];
+    if (tid < 12) {     // summed over the points in a fixed order (no float atomics: two runs of a guidance sampler have to agree)
+        float a = 0.f;
+        if (tid < 9) { for (int u = 0; u < H * Pv; ++u) a += red[16 + u * 6 + tid / 3] * red[16 + u * 6 + 3 + tid % 3]; dR[(size_t)bi * 9 + tid] += a; }
+        else { for (int u = 0; u < H * Pv; ++u) a -= sdg[u * 3 + tid - 9]; dT[(size_t)bi * 3 + tid - 9] += a; }
+    }
+    __syncthreads();                            // before the tile space is written
     {   // d att[h][j] = <d o[h], v_j> + <d o_pt[h], v_pt_j> + <d o_pair[h], p[b,i,j,:]>.  The pair rows come through LDS in tiles
         // of 64 (coalesced; a lane reading its own 512-B row channel by channel touches 64 lines per instruction); thread (j, wave)
         // accumulates heads wave, wave + 4, ... so that one LDS read of p feeds every head of the thread
@@ -1437,7 +1449,8 @@ static void launch_ipa_bwd_t(hipStream_t st, const IpaArgs& a, const IpaDims& d,
 void launch_ipa_bwd(hipStream_t st, const IpaArgs& a) {
     IpaDims d{a.B, a.N, a.H, a.C, a.Pq, a.Pv, a.cp, sqrtf(1.0f / (3.0f * a.C)), sqrtf(1.0f / 3.0f)};
     const size_t lds = ipa_train_lds(a.N, a.H, a.C, a.Pq, a.Pv, a.cp);
-    const size_t lds_q = lds + (size_t)64 * (a.cp + 1) * sizeof(float);            // + the staged tile of pair rows
+    // + the staged tile of pair rows (before it is staged, the space holds six floats per output point)
+    const size_t lds_q = lds + (size_t)std::max(64 * (a.cp + 1), a.H * a.Pv * 6) * sizeof(float);
     if (a.H == 12) launch_ipa_bwd_t<12>(st, a, d, lds, lds_q);
     else launch_ipa_bwd_t<0>(st, a, d, lds, lds_q);
 }

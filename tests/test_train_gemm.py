@@ -77,7 +77,10 @@ def test_misaligned_operands_and_odd_leading_dimensions():
         _check(c.cpu(), a64 @ b64, a64, b64, 3)
 
 
-@pytest.mark.parametrize('shape,nsplit', [((128, 128, 32768), 192), ((512, 128, 8192), 48), ((128, 256, 100000), 64), ((12, 128, 4096), 16), ((100, 67, 5000), 7)])
+# (the last three: launches of the training step at 16 928 and 6 272 pair rows whose trailing 7, 22 and 8 K ranges are EMPTY -- ranges are
+#  rounded up to whole 32-steps, so the last ones start past K -- on the 128-, 64- and 128-tile kernel with XCD renumbering and row sums)
+@pytest.mark.parametrize('shape,nsplit', [((128, 128, 32768), 192), ((512, 128, 8192), 48), ((128, 256, 100000), 64), ((12, 128, 4096), 16), ((100, 67, 5000), 7),
+                                          ((640, 128, 16928), 96), ((128, 128, 16928), 128), ((512, 128, 6272), 48)])
 def test_split_k_atomic_accumulation_and_row_sums(shape, nsplit):
     """the weight-gradient form: A = dY stored [K][M] (am 1), B = X stored [K][N], C += over splits; asum = column sums of dY"""
     capi, lib = _lib()
@@ -148,7 +151,7 @@ def test_two_piece_split_and_bad_arguments():
     assert lib.genie_train_gemm(None, C.byref(d), p(a.cuda()), p(b.cuda()), p(c), None, None, None) == -1      # split-K needs atomic mode
 
 
-@pytest.mark.parametrize('case', ['fwd_640', 'wgrad_640', 'fwd_small', 'wgrad_small'])
+@pytest.mark.parametrize('case', ['fwd_640', 'wgrad_640', 'fwd_small', 'wgrad_small', 'wgrad_640_empty'])
 def test_c_in_separately_placed_blocks(case):
     """Several Linears sharing an input as ONE GEMM: the product's column blocks (forward) or row blocks (weight gradients, split-K with
     row sums) land at separate places -- the tiled kernels take the block table, other shapes fall back to one GEMM per block."""
@@ -174,11 +177,12 @@ def test_c_in_separately_placed_blocks(case):
             got = buf[offs[k]:offs[k] + R * O].view(R, O).cpu().double()
             assert ((got - ref[:, k * O:(k + 1) * O]).abs() / scale[:, k * O:(k + 1) * O]).max().item() <= TOL[3]
     else:
-        R, K, O = (8192, 128, 128) if case == 'wgrad_640' else (200, 24, 24)
+        # wgrad_640_empty: 16 928 rows in 96 K ranges of 192 -- block rows placed by the table and 7 empty ranges in the same launch
+        R, K, O = {'wgrad_640': (8192, 128, 128), 'wgrad_640_empty': (16928, 128, 128), 'wgrad_small': (200, 24, 24)}[case]
         dy = torch.randn(R, nb * O, generator=g); x = torch.randn(R, K, generator=g)
         blob = torch.zeros(nb * (O * K + O) + 64, device='cuda')             # [w0 | b0 | w1 | b1 | ...] like a state_dict blob
         woff = [k * (O * K + O) for k in range(nb)]; boff = [k * (O * K + O) + O * K for k in range(nb)]
-        nsplit = 16 if case == 'wgrad_640' else 2
+        nsplit = {'wgrad_640': 16, 'wgrad_640_empty': 96, 'wgrad_small': 2}[case]
         d = capi.GenieGemmDesc(M=nb * O, N=K, K=R, batch=1, nb2=1, nsplit=nsplit, mode=2, terms=3, relu=0, am=1, ak=nb * O, bk=K, bn=1, cm=K, cn=1,
                                alpha=1.0, cblk=O, cblk_m=1)
         for k in range(nb): d.ctab[k] = woff[k]; d.atab[k] = boff[k]
