@@ -223,12 +223,28 @@ class GenieEngine:
         capi.check(self._h, rc, 'genie_p_sample')
         return rots
 
-    def sample_loop(self, noise, scale, quat_codes=None, first_step=None, last_step=1, state=None, record=False):
-        """noise [T,B,N,3] on device.  Returns (trans, rots, record or None)."""
+    def sample_loop(self, noise, scale, quat_codes=None, first_step=None, last_step=1, state=None, record=False, noise_first=0):
+        """noise [T,B,N,3] on device.  Returns (trans, rots, record or None).
+
+        genie_sample_loop indexes `noise` by the timestep, wherever it is entered: row 0 is the initial trans (read only when
+        first_step = T) and the landing of step t > 1 draws row T - t + 1, so a loop entered at first_step < T with `state` reads
+        rows T - first_step + 1 .. T - max(last_step, 2) + 1 and nothing before them.  `noise_first` = r says that `noise` holds
+        the rows from r on only (noise[k] is row r + k): the entry is handed the address row 0 would have, no T-row buffer is
+        allocated, and every row the loop will read is checked here to lie inside `noise`.  quat_codes are indexed by the
+        iteration (row 0 = the first iteration run) and are not affected."""
         T = self.dims['n_timestep']
         first_step = T if first_step is None else first_step
         noise = self._dev(noise, torch.float32)
         n_it = first_step - last_step + 1
+        noise_first = int(noise_first)
+        if 1 <= last_step <= first_step <= T:           # (the entry refuses anything else itself)
+            rows = [0] if first_step == T else []
+            rows += [T - t + 1 for t in (first_step, max(last_step, 2)) if max(last_step, 2) <= first_step]
+            if noise.dim() != 4 or tuple(noise.shape[1:]) != (self.B, self.N, 3) or noise_first < 0 or \
+                    any(not noise_first <= r < noise_first + noise.shape[0] for r in rows):
+                raise ValueError('noise must hold rows %s of the [%d, %d, %d, 3] layout for steps %d..%d, got %s starting at row %d'
+                                 % (sorted(set(rows)), T, self.B, self.N, first_step, last_step, tuple(noise.shape), noise_first))
+        noise_ptr = C.c_void_p(noise.data_ptr() - noise_first * self.B * self.N * 3 * 4)
         codes = self._dev(quat_codes, torch.int8) if quat_codes is not None else None
         if state is None:
             trans = torch.empty(self.B, self.N, 3, device=self.device)
@@ -236,7 +252,7 @@ class GenieEngine:
         else:
             trans, rots = state
         rec = torch.empty(n_it, self.B, self.N, 3, device=self.device) if record else None
-        rc = self.lib.genie_sample_loop(self._h, self._stream(), float(scale), _ptr(noise), _ptr(codes), first_step,
+        rc = self.lib.genie_sample_loop(self._h, self._stream(), float(scale), noise_ptr, _ptr(codes), first_step,
                                         last_step, _ptr(trans), _ptr(rots), _ptr(rec))
         capi.check(self._h, rc, 'genie_sample_loop')
         return trans, rots, rec

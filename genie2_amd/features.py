@@ -173,3 +173,68 @@ def create_np_features_from_motif_pdb(filepath):
     f['fixed_structure_mask'] = mask['structure']
     f['fixed_group'] = mask['group']
     return f
+
+
+def create_np_features_from_design(design_pdb, motif_pdb):
+    """The conditioning features a scaffold design was generated with, rebuilt from the two files a scaffold run writes for it
+    (not in the reference): `design_pdb` = pdbs/{name}.pdb (save_np_features_to_pdb) and `motif_pdb` = motif_pdbs/{name}.pdb
+    (motif.save_motif_pdb: the motif's ATOM records, residue index = 1-based position in the design, group in columns 73-76).
+    The same 12 keys as create_np_features_from_motif_pdb and, for the design that call produced, the same values, with no random
+    draw: the length comes from the design; fixed_sequence_mask, fixed_group and the group-wise fixed_structure_mask from the motif
+    file's residue indices and groups; aatype and the motif rows of atom_positions from its C-alpha records (in file order onto the
+    motif positions in ascending order, as create_np_features_from_motif_pdb places them); scaffold rows of atom_positions stay 0
+    (the design's own coordinates are the sampler's init_structure, not a feature).
+    A design whose length, motif positions or residue types disagree with the motif file is a ValueError naming the first mismatch."""
+    seqs, _ = parse_pdb(design_pdb)
+    if len(seqs) != 1:
+        raise ValueError('%s: a scaffold design has one chain, found %d' % (design_pdb, len(seqs)))
+    n = len(seqs[0])
+    marks = []                                      # the design's own group column, one entry per residue
+    with open(design_pdb) as fh:
+        for line in fh:
+            if line.startswith('ATOM') and line[13:15].strip() == 'CA':
+                marks.append(line[72:76].strip())
+    index, group, types, xyz = [], {}, [], []
+    with open(motif_pdb) as fh:
+        for line in fh:
+            if not line.startswith('ATOM'):
+                continue
+            i, g = int(line[22:26]), line[72:76].strip() or 'A'
+            if group.setdefault(i, g) != g:
+                raise ValueError('%s: residue %d is in group %s and in group %s' % (motif_pdb, i, group[i], g))
+            if line[13:15].strip() == 'CA':
+                index.append(i)
+                types.append(RESTYPE_ORDER[_RESTYPE_3_TO_1[line[17:20]]])
+                xyz.append([float(line[30:38]), float(line[38:46]), float(line[46:54])])
+    if not index:
+        raise ValueError('%s: no C-alpha ATOM record' % motif_pdb)
+    positions = sorted(group)
+    if len(set(index)) != len(index) or sorted(index) != positions:
+        raise ValueError('%s: every motif residue needs exactly one C-alpha record' % motif_pdb)
+    if positions[0] < 1 or positions[-1] > n:
+        raise ValueError('length: the motif file places residue %d, the design %s has residues 1..%d'
+                         % (positions[0] if positions[0] < 1 else positions[-1], design_pdb, n))
+    marked = [i + 1 for i, g in enumerate(marks) if g]
+    for i in sorted(set(marked) | set(positions)):
+        if i not in group or not marks[i - 1]:
+            raise ValueError('motif positions: residue %d is a motif residue in %s alone' % (i, motif_pdb if i in group else design_pdb))
+        if marks[i - 1] != group[i]:
+            raise ValueError('motif positions: residue %d is in group %s in the design and %s in the motif file' % (i, marks[i - 1], group[i]))
+    for i, t in zip(positions, types):
+        if seqs[0][i - 1] != t:
+            raise ValueError('residue types: residue %d is %s in the design and %s in the motif file'
+                             % (i, RESTYPE_3[seqs[0][i - 1]], RESTYPE_3[t]))
+    f = create_empty_np_features([n])
+    rows = np.array(positions) - 1
+    f['aatype'][rows] = np.eye(20)[types]
+    f['atom_positions'][rows] = np.array(xyz)
+    groups = np.zeros(n, dtype=int)
+    groups[rows] = [ord(group[i]) - ord('A') + 1 for i in positions]
+    structure = np.zeros((n, n))
+    for g in range(1, 1 + int(np.max(groups))):
+        m = groups == g
+        structure += m[:, None] * m[None, :]
+    f['fixed_sequence_mask'] = groups > 0
+    f['fixed_structure_mask'] = structure.astype(bool)
+    f['fixed_group'] = groups
+    return f

@@ -170,6 +170,22 @@ def respaced_steps(n_timestep, num_steps):
     return [int(v) for v in torch.round(torch.linspace(T, 1, K, dtype=torch.float64)).tolist()]
 
 
+def partial_steps(n_timestep, start_step, num_steps):
+    """The timesteps a `num_steps`-step reverse process visits when it is entered at `start_step` = t0 instead of T (partial
+    diffusion), strictly decreasing: rint(linspace(t0, 1, K)) in float64 exactly as respaced_steps forms its list, [t0] for K = 1,
+    t0, t0-1, ..., 1 for K = t0; partial_steps(T, T, K) == respaced_steps(T, K)."""
+    T = int(n_timestep)
+    if isinstance(start_step, bool) or int(start_step) != start_step or not 1 <= int(start_step) <= T:
+        raise ValueError('start_step must be an integer in 1..%d, got %r' % (T, start_step))
+    t0 = int(start_step)
+    if isinstance(num_steps, bool) or int(num_steps) != num_steps or not 1 <= int(num_steps) <= t0:
+        raise ValueError('num_steps must be an integer in 1..%d with start_step=%d, got %r' % (t0, t0, num_steps))
+    K = int(num_steps)
+    if K == 1:
+        return [t0]
+    return [int(v) for v in torch.round(torch.linspace(t0, 1, K, dtype=torch.float64)).tolist()]
+
+
 def check_sampler(sampler, eta=None):
     """The (sampler, eta) pair of the few-step samplers: eta belongs to 'ddim' alone, in [0, 1]; None is its default 0."""
     if sampler not in SAMPLERS:

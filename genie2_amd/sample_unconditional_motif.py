@@ -19,15 +19,17 @@ rigid motif.
 
 `--num_particles K` makes every design a particle system of its own: `--num_samples` then counts designs, `--batch_size` designs per
 sampler call (a device batch of batch_size * K particles), and each system's best particle (the largest accumulated weight) is the
-one written, one PDB and one location file per design.  Without it a batch is one system and every particle is written."""
-import argparse
+one written, one PDB and one location file per design.  Without it a batch is one system and every particle is written.
+
+`--input_pdb FILE --start_step T0` starts every particle from the file's backbone noised to step T0 (partial diffusion, as in the
+unconditional CLI: one length, `--write_start_rmsd`); it combines with `--align`, `--motif_groups`, `--num_particles` and `--num_steps`."""
 import os
 
 from tqdm import tqdm
 
 from .diffusion import load_pretrained_model
 from .motif import load_motif_spec
-from .sample_unconditional import UnconditionalRunner
+from .sample_unconditional import PartialParser, UnconditionalRunner, write_start_rmsd
 
 
 def load_motif_segments(filepath):
@@ -118,14 +120,17 @@ class MotifRunner(UnconditionalRunner):
                     'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
                     'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
-                    'num_steps': constants.get('num_steps'), **systems})
+                    'num_steps': constants.get('num_steps'), **systems, **self.partial_params(constants)})
+                if constants.get('write_start_rmsd'):
+                    write_start_rmsd(sampler.last_start_rmsd, os.path.join(constants['outdir'], 'start_rmsd'),
+                                     ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
                 if constants['write_motif_locations']:
                     write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
                 remaining -= batch
 
 
 def build_parser():
-    p = argparse.ArgumentParser()
+    p = PartialParser('input_pdb', 'Structure file whose C-alpha backbone every particle starts from')
     p.add_argument('--name', type=str, help='Model name', required=True)
     p.add_argument('--epoch', type=int, help='Model epoch', required=True)
     p.add_argument('--rootdir', type=str, help='Root directory', default='results')

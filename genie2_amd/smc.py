@@ -14,7 +14,7 @@ import torch
 
 from . import features as F
 from . import pack
-from .sampler import UnconditionalSampler
+from .sampler import UnconditionalSampler, start_rmsd
 
 
 def normalize_log_weights(log_weights, dim):
@@ -138,7 +138,18 @@ class TwistedSampler(UnconditionalSampler):
     is a scalar for every system or S values; `ess_trace` is a CPU tensor [steps - 1, S], `resampled_at` a list of S lists of steps,
     `last_log_weights` [S, K] the accumulated log-weights after the last weight update and `last_choice` [S] their argmax (the lowest
     index of equal ones).  'return_particles': 'all' (default) returns the S K structures, 'best' particle last_choice[s] of every
-    system (S structures, `last_fit` with S rows).  Without 'num_particles' nothing of this applies: one system of num_samples."""
+    system (S structures, `last_fit` with S rows).  Without 'num_particles' nothing of this applies: one system of num_samples.
+
+    Partial diffusion ('init_structure' + 'start_step' = t0, the sampler module's docstring; not in the reference): the particles
+    start at x_t0 = c0 x_in + c1 noise[0] (genie_q_sample, its frames) and visit t0, ..., 1, or pack.partial_steps(T, t0, K) with
+    pack.twisted_coefficients; 'noise' is [n, B, N, 3] for n visited steps, noise[0] the forward draw.  With particle systems an
+    [N, 3] start is shared by all particles of all systems and an [S K, N, 3] start is system-major like everything else.
+    The initial log_proposal is log_normal_density(noise[0], 0, 1).sum(dim=(1, 2)): the density of the actual proposal
+    q(x_t0 | x_in) = N(c0 x_in, c1^2) at x_t0 is that of noise[0] under N(0, 1) minus 3 N log c1, a constant that is equal for all
+    particles and cancels in every normalisation the loop performs (softmax, normalize_log_weights, the ESS).  With t0 = T it is
+    today's expression to within c0 ~ 1.6e-3.  `ess_trace` (n - 1 entries), `resampled_at`, `last_unguided_steps` and the
+    potential's `step` argument stay defined on the timestep itself.  'sampler': 'ddim' stays refused.  `last_start_rmsd` [B] is
+    set as in BaseSampler (every returned structure against the start of its own batch slot, whichever ancestor it was resampled from)."""
 
     def __init__(self, model):
         if getattr(model.model, 'dims', {}).get('n_head_tri', 0):       # before any device work
@@ -156,12 +167,13 @@ class TwistedSampler(UnconditionalSampler):
         if params.get('num_particles') is not None or params.get('return_particles') is not None:
             return self._sample_systems(params)
         plan = self.few_step_plan(params)
-        feats = F.convert_np_features_to_tensor(
-            F.batchify_np_features([self.create_np_features(params) for _ in range(params['num_samples'])]), self.device)
-        B, N = feats['residue_mask'].shape
         m = self.model
         T = m.config.diffusion['n_timestep']
-        steps = list(range(T, 0, -1)) if plan is None else plan[0]
+        steps = list(range(self.partial_start(params) or T, 0, -1)) if plan is None else plan[0]
+        np_feats = F.batchify_np_features([self.create_np_features(params) for _ in range(params['num_samples'])])
+        partial = self.partial_inputs(params, np_feats, len(steps))
+        feats = F.convert_np_features_to_tensor(np_feats, self.device)
+        B, N = feats['residue_mask'].shape
         tw_coef = None if plan is None else plan[1].to(device=self.device, dtype=torch.float32)
         sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(T).items()}
         abar, betas = sched['alphas_cumprod'], sched['betas']
@@ -182,7 +194,10 @@ class TwistedSampler(UnconditionalSampler):
         trans = draw(0)
         log_proposal = log_normal_density(trans, torch.tensor(0., device=self.device), torch.tensor(1., device=self.device)).sum(dim=(1, 2))
         log_w_acc = torch.zeros(B, device=self.device)
-        rots = eng.frenet(trans)
+        if partial is None:
+            rots = eng.frenet(trans)
+        else:           # trans was the forward draw noise[0]: log_proposal is its density (the class docstring), the state q_sample's
+            trans, rots = self.start_state(eng, partial[1], trans.float() * mask, partial[0])
         self.ess_trace, self.resampled_at = [], []
         us = list(params.get('resample_u', []))
         for it, step in enumerate(steps):
@@ -230,6 +245,7 @@ class TwistedSampler(UnconditionalSampler):
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans.detach()).items()}
         feats['atom_positions'] = trans.detach().cpu()
+        self.last_start_rmsd = None if partial is None else start_rmsd(feats['atom_positions'], partial[1], feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 
     def _sample_systems(self, params):
@@ -246,7 +262,7 @@ class TwistedSampler(UnconditionalSampler):
         plan = self.few_step_plan(params)
         m = self.model
         T = m.config.diffusion['n_timestep']
-        steps = list(range(T, 0, -1)) if plan is None else plan[0]
+        steps = list(range(self.partial_start(params) or T, 0, -1)) if plan is None else plan[0]
         noise = params.get('noise')
         if noise is not None and (noise.dim() != 4 or noise.shape[0] != len(steps) or noise.shape[1] != S * K):
             raise ValueError('noise must be [%d, %d, N, 3] with num_samples=%d and num_particles=%d, got %s'
@@ -255,8 +271,9 @@ class TwistedSampler(UnconditionalSampler):
         us = [[float(e)] * S if _is_scalar(e) else [float(v) for v in e] for e in us]
         if any(len(e) != S for e in us):
             raise ValueError('an entry of resample_u is a scalar or %d values, one per system' % S)
-        feats = F.convert_np_features_to_tensor(
-            F.batchify_np_features([self.create_np_features(params) for _ in range(S * K)]), self.device)
+        np_feats = F.batchify_np_features([self.create_np_features(params) for _ in range(S * K)])
+        partial = self.partial_inputs(params, np_feats, len(steps))
+        feats = F.convert_np_features_to_tensor(np_feats, self.device)
         B, N = feats['residue_mask'].shape
         tw_coef = None if plan is None else plan[1].to(device=self.device, dtype=torch.float32)
         sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(T).items()}
@@ -278,7 +295,10 @@ class TwistedSampler(UnconditionalSampler):
         trans = draw(0)
         log_proposal = log_normal_density(trans, torch.tensor(0., device=self.device), torch.tensor(1., device=self.device)).sum(dim=(1, 2))
         log_w_acc = torch.zeros(B, device=self.device)
-        rots = eng.frenet(trans)
+        if partial is None:
+            rots = eng.frenet(trans)
+        else:           # trans was the forward draw noise[0]: log_proposal is its density (the class docstring), the state q_sample's
+            trans, rots = self.start_state(eng, partial[1], trans.float() * mask, partial[0])
         reweight = SmcReweight(S, K, N, self.device)
         ess_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.float32, device=self.device)
         resampled_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.int32, device=self.device)
@@ -323,14 +343,17 @@ class TwistedSampler(UnconditionalSampler):
         first = torch.where(top, torch.arange(K).expand(S, K), torch.full((S, K), K)).min(dim=1).values
         self.last_choice = torch.where(first < K, first, torch.zeros_like(first))       # (no entry equals a NaN max: particle 0)
         trans = trans.detach()
+        start = None if partial is None else partial[1]
         if keep == 'best':
             pick = (torch.arange(S) * K + self.last_choice).to(self.device)
             trans = trans[pick]
+            start = None if start is None else start[pick.cpu()]
             feats = {k: (v[pick] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for k, v in feats.items()}
         self.last_fit = None
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans).items()}
         feats['atom_positions'] = trans.cpu()
+        self.last_start_rmsd = None if start is None else start_rmsd(feats['atom_positions'], start, feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 
 

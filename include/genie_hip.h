@@ -258,7 +258,12 @@ int genie_p_sample(genie_handle_t h, genie_stream_t stream, int step, float scal
  * noise [n_timestep][B,N,3]: noise[0] is the initial trans (base.py:227),
  * noise[k] the draw of iteration k (steps T..2).  first_step/last_step allow a
  * partial trajectory (T..1 for the full one); when first_step < T,
- * trans_io/rots_io carry the state in.  quat_codes: NULL or
+ * trans_io/rots_io carry the state in.  noise is indexed by the timestep and
+ * not by the iteration: the landing of step t > 1 draws noise[T - t + 1]
+ * wherever the loop was entered, noise[0] is read only when first_step == T,
+ * and a loop entered at first_step < T reads rows T - first_step + 1 ..
+ * T - max(last_step, 2) + 1 alone (the caller may pass the address row 0
+ * would have without owning the rows before them).  quat_codes: NULL or
  * [n_iterations][B,N,N].  record: NULL or [n_iterations][B,N,3], x after
  * every iteration. */
 int genie_sample_loop(genie_handle_t h, genie_stream_t stream, float scale,
