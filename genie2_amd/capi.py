@@ -109,9 +109,13 @@ SYMBOLS = {
     'genie_smc_reweight': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double] + [C.c_void_p] * 7 +
                            [C.c_size_t]),
     'genie_smc_reweight_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'genie_shape_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
+                                         C.c_int] + [C.c_void_p] * 10 + [C.c_size_t]),
+    'genie_shape_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
+SHAPE_REPORT = ('rog', 'min_distance', 'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation')      # GENIE_SHAPE_REPORT slots
 
 _lib = None
 

@@ -22,7 +22,12 @@ sampler call (a device batch of batch_size * K particles), and each system's bes
 one written, one PDB and one location file per design.  Without it a batch is one system and every particle is written.
 
 `--input_pdb FILE --start_step T0` starts every particle from the file's backbone noised to step T0 (partial diffusion, as in the
-unconditional CLI: one length, `--write_start_rmsd`); it combines with `--align`, `--motif_groups`, `--num_particles` and `--num_steps`."""
+unconditional CLI: one length, `--write_start_rmsd`); it combines with `--align`, `--motif_groups`, `--num_particles` and `--num_steps`.
+
+`--rog_max`, `--clash_distance` and `--restraint_file` (with their weights, `--clash_separation` and `--shape_tausq`: the flags of
+genie2_amd/sample_unconditional_shape.py) add shape guidance: the potential is then SumPotential(MotifPotential, ShapePotential), and
+`--write_shape_report` writes outdir/shape/{length}_{index}.txt as that CLI does.  Lengths too short for a restrained residue are
+skipped."""
 import os
 
 from tqdm import tqdm
@@ -30,6 +35,8 @@ from tqdm import tqdm
 from .diffusion import load_pretrained_model
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, write_start_rmsd
+from .sample_unconditional_shape import (add_shape_arguments, restrained_lengths, shape_constants, shape_potential,
+                                         write_shape_report)
 
 
 def load_motif_segments(filepath):
@@ -79,7 +86,8 @@ class MotifRunner(UnconditionalRunner):
         short = [t['length'] for t in tasks if t['length'] < total]
         if short:
             print('skipping lengths shorter than the {}-residue motif: {}'.format(total, ', '.join(map(str, short))))
-        return [t for t in tasks if t['length'] >= total]
+        tasks = [t for t in tasks if t['length'] >= total]
+        return restrained_lengths(tasks, shape_constants(params)['restraints'])
 
     def create_constants(self, params):
         c = super().create_constants(params)
@@ -90,15 +98,17 @@ class MotifRunner(UnconditionalRunner):
         c['motif_groups'] = params.get('motif_groups', 'joint')
         c['groups'] = load_motif_groups(params['motif_file']) if c['motif_groups'] == 'file' else None
         c['num_particles'] = params.get('num_particles')
+        c.update(shape_constants(params))
         return c
 
     def execute(self, constants, tasks, device):
         from . import pack
-        from .smc import MotifPotential, TwistedSampler
+        from .smc import MotifPotential, SumPotential, TwistedSampler
         model = load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
         sampler = TwistedSampler(model)
         abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
         for task in tqdm(tasks, desc=device):
+            shape = shape_potential(constants, task['length'], abar, device)
             remaining = constants['num_samples']
             while remaining > 0:
                 batch = min(constants['batch_size'], remaining)
@@ -112,6 +122,8 @@ class MotifRunner(UnconditionalRunner):
                 potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
                                            max_offsets=constants['max_offsets'], device=device, align=constants['align'],
                                            groups=constants.get('groups'))
+                if shape is not None:
+                    potential = SumPotential(potential, shape)
                 # (with --num_particles: `batch` systems, each returning its best particle)
                 systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'],
                                                                              'return_particles': 'best'}
@@ -126,6 +138,8 @@ class MotifRunner(UnconditionalRunner):
                                      ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
                 if constants['write_motif_locations']:
                     write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
+                if constants['write_shape_report'] and shape is not None:
+                    write_shape_report(sampler.last_shape, os.path.join(constants['outdir'], 'shape'), task['length'], offset)
                 remaining -= batch
 
 
@@ -170,6 +184,7 @@ def build_parser():
                    help='Guide every design as a particle system of its own with this many particles (1..64) and write its best '
                         'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
                         'written (an addition to the reference CLI, like --align)')
+    add_shape_arguments(p)
     return p
 
 

@@ -1,0 +1,172 @@
+"""`python -m genie2_amd.sample_unconditional_shape` -- shape-guided twisted-diffusion / SMC sampling (not in the reference): the
+unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
+(genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
+closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
+least one of the three is needed.
+
+The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
+Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
+
+`--write_shape_report` adds outdir/shape/{length}_{index}.txt beside each PDB, one `key value` line per report field of the written
+structure: rog, min_distance, n_clash, e_rog, e_clash, e_restraint, n_violated, max_violation (ShapePotential.describe).
+
+`--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
+`--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
+add_shape_arguments too and then guides with the sum of both potentials."""
+import os
+
+from tqdm import tqdm
+
+from .sample_unconditional import PartialParser, UnconditionalRunner, write_start_rmsd
+
+SHAPE_KEYS = ('rog_max', 'rog_weight', 'clash_distance', 'clash_separation', 'clash_weight', 'shape_tausq')
+COUNTS = ('n_clash', 'n_violated')
+
+
+def add_shape_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --align)'
+    parser.add_argument('--rog_max', type=float, default=None,
+                        help='Guide the radius of gyration below this many Angstrom; default: no such term' + tail)
+    parser.add_argument('--rog_weight', type=float, default=1.0, help='Weight of the radius-of-gyration term' + tail)
+    parser.add_argument('--clash_distance', type=float, default=None,
+                        help='Guide C-alpha pairs apart that are closer than this many Angstrom; default: no such term' + tail)
+    parser.add_argument('--clash_separation', type=int, default=2,
+                        help='Residues at least this far apart in sequence count as a clashing pair' + tail)
+    parser.add_argument('--clash_weight', type=float, default=1.0, help='Weight of the clash term' + tail)
+    parser.add_argument('--restraint_file', type=str, default=None,
+                        help='Distance restraints, one `i j lo hi [weight]` line each (0-based residues, Angstrom)' + tail)
+    parser.add_argument('--shape_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the shape terms, Angstrom^2' + tail)
+    parser.add_argument('--write_shape_report', action='store_true',
+                        help='Write outdir/shape/{length}_{index}.txt: radius of gyration, closest pair, clashes, energies and '
+                             'restraint violations of every written structure' + tail)
+
+
+def shape_constants(params):
+    """The shape keys of a runner's constants: the flags of add_shape_arguments, the restraint file read into 'restraints'."""
+    from .smc import load_restraints
+    defaults = dict(rog_max=None, rog_weight=1.0, clash_distance=None, clash_separation=2, clash_weight=1.0, shape_tausq=1.0)
+    c = {k: params.get(k, defaults[k]) for k in SHAPE_KEYS}
+    c['restraints'] = load_restraints(params['restraint_file']) if params.get('restraint_file') else []
+    c['write_shape_report'] = bool(params.get('write_shape_report', False))
+    return c
+
+
+def has_shape_terms(constants):
+    return constants.get('rog_max') is not None or constants.get('clash_distance') is not None or bool(constants.get('restraints'))
+
+
+def restrained_lengths(tasks, restraints):
+    """The tasks long enough for every restrained residue; the others are skipped with one printed line."""
+    need = 1 + max([max(r[0], r[1]) for r in restraints], default=-1)
+    short = [t['length'] for t in tasks if t['length'] < need]
+    if short:
+        print('skipping lengths shorter than the {} residues the restraints name: {}'.format(need, ', '.join(map(str, short))))
+    return [t for t in tasks if t['length'] >= need]
+
+
+def shape_potential(constants, length, abar, device):
+    """The ShapePotential the constants ask for at this length, or None when they ask for no term.  (Lengths too short for a
+    restrained residue never get here: restrained_lengths drops them when the tasks are made.)"""
+    if not has_shape_terms(constants):
+        return None
+    from .smc import ShapePotential
+    return ShapePotential(length, abar, rog_max=constants['rog_max'], rog_weight=constants['rog_weight'],
+                          clash_distance=constants['clash_distance'], clash_separation=constants['clash_separation'],
+                          clash_weight=constants['clash_weight'], restraints=constants['restraints'] or None,
+                          tausq=constants['shape_tausq'], device=device)
+
+
+def write_shape_report(last_shape, directory, length, offset):
+    """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: a `key value` line per field
+    of TwistedSampler.last_shape, %.3f for Angstrom and energies, %d for counts."""
+    os.makedirs(directory, exist_ok=True)
+    for i in range(len(next(iter(last_shape.values())))):
+        with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
+            for key, column in last_shape.items():
+                fh.write(('{} {:d}\n' if key in COUNTS else '{} {:.3f}\n').format(key, column[i].item()))
+
+
+class ShapeRunner(UnconditionalRunner):
+    def create_tasks(self, params):
+        from .smc import load_restraints
+        restraints = load_restraints(params['restraint_file']) if params.get('restraint_file') else []
+        return restrained_lengths(super().create_tasks(params), restraints)
+
+    def create_constants(self, params):
+        c = super().create_constants(params)
+        c.update({k: params[k] for k in ('guidance_alpha', 'ess_threshold', 'last_unguided_steps')})
+        c['num_particles'] = params.get('num_particles')
+        c.update(shape_constants(params))
+        if not has_shape_terms(c):
+            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file')
+        return c
+
+    def execute(self, constants, tasks, device):
+        from . import pack
+        from .smc import TwistedSampler
+        model = self.load_model(constants, device)
+        sampler = TwistedSampler(model)
+        abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
+        for task in tqdm(tasks, desc=device):
+            potential = shape_potential(constants, task['length'], abar, device)
+            remaining = constants['num_samples']
+            while remaining > 0:
+                batch = min(constants['batch_size'], remaining)
+                offset = constants['num_samples'] - remaining
+                if constants.get('resume') and all(
+                        os.path.exists(os.path.join(constants['outdir'], 'pdbs', '{}_{}.pdb'.format(task['length'], offset + i)))
+                        for i in range(batch)):
+                    remaining -= batch           # this batch was written by an earlier (interrupted) run
+                    continue
+                # (with --num_particles: `batch` systems, each returning its best particle)
+                systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'],
+                                                                             'return_particles': 'best'}
+                sampler.sample({
+                    'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
+                    'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
+                    'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
+                    'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
+                    'num_steps': constants.get('num_steps'), **systems, **self.partial_params(constants)})
+                if constants.get('write_start_rmsd'):
+                    write_start_rmsd(sampler.last_start_rmsd, os.path.join(constants['outdir'], 'start_rmsd'),
+                                     ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
+                if constants['write_shape_report']:
+                    write_shape_report(sampler.last_shape, os.path.join(constants['outdir'], 'shape'), task['length'], offset)
+                remaining -= batch
+
+
+def build_parser():
+    p = PartialParser('input_pdb', 'Structure file whose C-alpha backbone every particle starts from')
+    p.add_argument('--name', type=str, help='Model name', required=True)
+    p.add_argument('--epoch', type=int, help='Model epoch', required=True)
+    p.add_argument('--rootdir', type=str, help='Root directory', default='results')
+    p.add_argument('--scale', type=float, help='Sampling noise scale', required=True)
+    p.add_argument('--outdir', type=str, help='Output directory', required=True)
+    p.add_argument('--num_samples', type=int, help='Number of samples per length', default=5)
+    p.add_argument('--batch_size', type=int, help='Batch size', default=4)
+    p.add_argument('--min_length', type=int, help='Minimum sequence length', default=50)
+    p.add_argument('--max_length', type=int, help='Maximum sequence length', default=256)
+    p.add_argument('--length_step', type=int, help='Length step size', default=1)
+    p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
+    p.add_argument('--sequential_order', action='store_true', help='Run in increasing order of length')
+    p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist')
+    p.add_argument('--guidance_alpha', type=float, default=0.012, help='Guidance gradient regulariser alpha')
+    p.add_argument('--ess_threshold', type=float, default=0.5,
+                   help='Resample when the effective sample size falls below this fraction of the batch')
+    p.add_argument('--last_unguided_steps', type=int, default=50, help='Steps below this one are not guided')
+    p.add_argument('--num_steps', type=int, default=None,
+                   help='Run the reverse process on this many of the n_timestep steps, with the ancestral kernel between them; default: all')
+    p.add_argument('--num_particles', type=int, default=None,
+                   help='Guide every design as a particle system of its own with this many particles (1..64) and write its best '
+                        'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
+                        'written')
+    add_shape_arguments(p)
+    return p
+
+
+def main(args):
+    ShapeRunner().run(vars(args), args.num_devices, args.sequential_order)
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

@@ -3,7 +3,8 @@
 function, :465-576 the loop) without its wandb / file logging.  The gradient torch.autograd takes there through the whole
 Denoiser is `GenieEngine.denoise_vjp` here (HIP backward kernels, frames held fixed exactly as `T(rots.detach(), trans.detach())`
 does); the reference's potential acts on a [B, N, 3] tensor and stays in PyTorch here (motif_twisting_function), with
-MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).
+MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).  ShapePotential (csrc/shape_kernels.hip: radius of
+gyration, clashes, distance restraints; not in the reference) is the second built-in potential and SumPotential adds potentials.
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -124,7 +125,9 @@ class TwistedSampler(UnconditionalSampler):
     'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50).
     After _sample, `last_fit` holds what the twisting function's `locate` says of the final coordinates (MotifPotential.locate: 'best',
     'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample; with motif groups also 'group_rmsd' and the 'groups' labels),
-    or None when it has no `locate`.
+    or None when it has no `locate`; `last_shape` what its `describe` says of them (ShapePotential.describe: 'rog', 'min_distance',
+    'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation' as CPU tensors, one row per returned sample), or None
+    when it has no `describe`.
     Optional 'num_steps' = K (not in the reference) visits the K timesteps of pack.respaced_steps with the ancestral kernel between
     them (pack.twisted_coefficients): `ess_trace` then has K - 1 entries, the last visited step takes the role of step 1, and
     `last_unguided_steps` and the potential keep reading the timestep itself.  'sampler': 'ddim' is refused (ValueError): the
@@ -244,6 +247,7 @@ class TwistedSampler(UnconditionalSampler):
         self.last_fit = None
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans.detach()).items()}
+        self.last_shape = {k: v.cpu() for k, v in twist.describe(trans.detach()).items()} if hasattr(twist, 'describe') else None
         feats['atom_positions'] = trans.detach().cpu()
         self.last_start_rmsd = None if partial is None else start_rmsd(feats['atom_positions'], partial[1], feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
@@ -352,6 +356,7 @@ class TwistedSampler(UnconditionalSampler):
         self.last_fit = None
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans).items()}
+        self.last_shape = {k: v.cpu() for k, v in twist.describe(trans).items()} if hasattr(twist, 'describe') else None
         feats['atom_positions'] = trans.cpu()
         self.last_start_rmsd = None if start is None else start_rmsd(feats['atom_positions'], start, feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
@@ -613,3 +618,203 @@ class MotifPotential:
             from . import capi
             raise capi.GenieError('%s failed (%d)' % (name, rc))
         return tuple(t for t in outs if t is not None)
+
+
+def load_restraints(path):
+    """A restraint file -> [(i, j, lo, hi, weight), ...] for ShapePotential: one restraint per line, `i j lo hi [weight]`, residues
+    0-based like the motif_locations files, distances in Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment,
+    blank lines are ignored.  A bad line raises ValueError('<path>:<line number>: ...')."""
+    out = []
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            fields = line.split('#', 1)[0].split()
+            if not fields:
+                continue
+            if len(fields) not in (4, 5):
+                raise ValueError('%s:%d: expected `i j lo hi [weight]`, got %d fields' % (path, number, len(fields)))
+            try:
+                i, j = int(fields[0]), int(fields[1])
+                lo, hi = float(fields[2]), float(fields[3])
+                weight = float(fields[4]) if len(fields) == 5 else 1.0
+            except ValueError:
+                raise ValueError('%s:%d: residues are integers, lo, hi and weight numbers: %r' % (path, number, line.strip())) from None
+            out.append((i, j, lo, hi, weight))
+    return out
+
+
+def check_restraints(restraints, n_res):
+    """The restraints of ShapePotential, validated on the host: [(i, j, lo, hi, weight), ...] with i != j, both in 0..n_res-1,
+    0 <= lo <= hi (hi may be inf), weight finite and >= 0 (1 when omitted), no pair listed twice in either order."""
+    import math
+    out, seen = [], set()
+    for k, r in enumerate(restraints):
+        r = tuple(r)
+        if len(r) not in (4, 5):
+            raise ValueError('restraint %d: expected (i, j, lo, hi[, weight]), got %r' % (k, r))
+        i, j = r[0], r[1]
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in (i, j)):
+            raise ValueError('restraint %d: residues must be integers, got %r and %r' % (k, i, j))
+        i, j, lo, hi, weight = int(i), int(j), float(r[2]), float(r[3]), float(r[4]) if len(r) == 5 else 1.0
+        if i == j:
+            raise ValueError('restraint %d: residue %d is restrained to itself' % (k, i))
+        if not (0 <= i < n_res and 0 <= j < n_res):
+            raise ValueError('restraint %d: residues %d and %d must lie in 0..%d' % (k, i, j, n_res - 1))
+        if not (0 <= lo <= hi) or math.isinf(lo):
+            raise ValueError('restraint %d: needs 0 <= lo <= hi with lo finite, got lo = %r, hi = %r' % (k, lo, hi))
+        if not (math.isfinite(weight) and weight >= 0):
+            raise ValueError('restraint %d: the weight must be finite and >= 0, got %r' % (k, weight))
+        if (min(i, j), max(i, j)) in seen:
+            raise ValueError('restraint %d: the pair (%d, %d) is listed twice' % (k, i, j))
+        seen.add((min(i, j), max(i, j)))
+        out.append((i, j, lo, hi, weight))
+    return out
+
+
+def restraint_table(restraints, n_res):
+    """The per-residue table genie_shape_potential takes, as CPU tensors (offset int32 [n_res + 1], partner int32 [R2], lo, hi, weight
+    f32 [R2]): every restraint at both of its residues, a residue's entries at offset[n] .. offset[n + 1] - 1 with ascending partners."""
+    entries = sorted([(i, j, lo, hi, w) for i, j, lo, hi, w in restraints] + [(j, i, lo, hi, w) for i, j, lo, hi, w in restraints])
+    offset = [0] * (n_res + 1)
+    for e in entries:
+        offset[e[0] + 1] += 1
+    for n in range(n_res):
+        offset[n + 1] += offset[n]
+    f32 = lambda k: torch.tensor([e[k] for e in entries], dtype=torch.float32)      # noqa: E731
+    return (torch.tensor(offset, dtype=torch.int32), torch.tensor([e[1] for e in entries], dtype=torch.int32), f32(2), f32(3), f32(4))
+
+
+class _ShapePotentialFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, pot, var):
+        logp, grad = pot._launch(pot._checked(x0), var)
+        ctx.save_for_backward(grad)
+        return logp
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        grad, = ctx.saved_tensors
+        return grad_output[:, None, None] * grad, None, None
+
+
+class ShapePotential:
+    """Shape guidance as one HIP pass (genie_shape_potential, csrc/shape_kernels.hip; include/genie_hip.h states the mathematics):
+    `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside MotifPotential
+    (SumPotential adds them).  Three terms, each a squared hinge in Angstrom:
+      rog_max          a cap on the radius of gyration (None: off), weighted rog_weight;
+      clash_distance   every pair of residues at least clash_separation apart in sequence closer than this (None: off), weighted
+                       clash_weight;
+      restraints       [(i, j, lo, hi[, weight]), ...], 0-based residues like the motif_locations files: the distance of i and j is
+                       kept in lo..hi (hi may be inf, lo may be 0); load_restraints reads them from a file.
+    log p = -(E_rog + E_clash + E_rst) / (2 var), var = xstart_variance(alphas_cumprod[step], tausq) computed on the device, so nothing
+    on the per-step path reads device memory from the host; the forward keeps the gradient the kernel computes and the backward
+    scales it.  The likelihood is unnormalised (the sampler only uses differences and normalised weights).
+
+    The restraints are validated on the host (check_restraints) before the device is looked at; the per-residue table is built and
+    uploaded once.  A potential with no term enabled is a ValueError.  `describe(x)` reports every sample of x: 'rog', 'min_distance'
+    (over the eligible pairs; inf when there is none), 'n_clash' (int64), 'e_rog', 'e_clash', 'e_restraint' (the weighted energies,
+    before the division by 2 var), 'n_violated' (int64), 'max_violation', [B] tensors on the potential's device.
+
+    The defaults (tausq = 1 A^2, separation 2, weights 1) are design choices: no trained checkpoint is in the tree, so their effect on
+    sample quality is unmeasured."""
+
+    def __init__(self, n_res, alphas_cumprod, rog_max=None, rog_weight=1.0, clash_distance=None, clash_separation=2, clash_weight=1.0,
+                 restraints=None, tausq=1.0, device='cuda'):
+        import math
+        from . import capi
+        self.n_res = int(n_res)
+        if self.n_res < 1:
+            raise ValueError('n_res must be at least 1, got %r' % (n_res,))
+        if rog_max is None and clash_distance is None and not restraints:
+            raise ValueError('no term enabled: give rog_max, clash_distance or restraints')
+        for name, v in (('rog_max', rog_max), ('rog_weight', rog_weight), ('clash_distance', clash_distance), ('clash_weight', clash_weight)):
+            if v is not None and not (math.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, v))
+        if isinstance(clash_separation, bool) or not isinstance(clash_separation, numbers.Integral) or clash_separation < 1:
+            raise ValueError('clash_separation must be an integer >= 1, got %r' % (clash_separation,))
+        if not (math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        # a term that is off is a weight of 0 to the entry
+        self.rog_max, self.rog_weight = (0.0, 0.0) if rog_max is None else (float(rog_max), float(rog_weight))
+        self.clash_distance, self.clash_weight = (0.0, 0.0) if clash_distance is None else (float(clash_distance), float(clash_weight))
+        self.clash_separation, self.tausq = int(clash_separation), float(tausq)
+        self.restraints = check_restraints(restraints or [], self.n_res)
+        table = restraint_table(self.restraints, self.n_res)
+        self.lib = capi.load_library()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise capi.GenieError('ShapePotential runs on the GPU (libgenie_hip); there is no CPU path')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.R2 = int(table[1].numel())
+        self.table = tuple(t.to(self.device) for t in table) if self.R2 else (None,) * 5
+        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
+        self._work = torch.zeros(0, dtype=torch.float32, device=self.device)
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+
+    def variance(self, step):
+        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
+
+    def __call__(self, x0, step):
+        return _ShapePotentialFn.apply(x0, self, self.variance(step))
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        from . import capi
+        report, = self._launch(self._checked(x), self._one, report=True)                   # (the energies do not depend on var)
+        counts = ('n_clash', 'n_violated')
+        return {k: report[:, i].round().long() if k in counts else report[:, i].clone() for i, k in enumerate(capi.SHAPE_REPORT)}
+
+    def _checked(self, x0):
+        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
+            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
+        if x0.device != self.device:
+            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
+        return x0.detach().to(torch.float32).contiguous()
+
+    def _launch(self, x, var, report=False):
+        """One call of the C entry on x (f32, contiguous): (report [B, 8],) when `report`, else (logp, grad)."""
+        import ctypes as C
+        from . import capi
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        if report:
+            outs = [None, None, torch.empty(B, len(capi.SHAPE_REPORT), **f32)]
+        else:
+            outs = [torch.empty(B, **f32), torch.empty_like(x), None]
+        need = self.lib.genie_shape_potential_work_bytes(B, self.n_res)
+        if need > self._work.numel() * 4:
+            self._work = torch.empty(need // 4, **f32)
+        with torch.cuda.device(x.device):
+            rc = self.lib.genie_shape_potential(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
+                                                self.rog_max, self.rog_weight, self.clash_distance, self.clash_separation,
+                                                self.clash_weight, self.R2, *(p(t) for t in self.table), p(var),
+                                                *(p(t) for t in outs), p(self._work), self._work.numel() * 4)
+        if rc != 0:
+            msg = self.lib.genie_last_error(None)
+            raise capi.GenieError('genie_shape_potential failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        return tuple(t for t in outs if t is not None)
+
+
+class SumPotential:
+    """The sum of twisting functions: `SumPotential(a, b, ...)(x0, step) = a(x0, step) + b(x0, step) + ...`, added in that order.
+    `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential), `describe` that of the first member
+    that has one (ShapePotential); an attribute no member has is absent, so TwistedSampler's hasattr checks see through the sum."""
+
+    def __init__(self, *potentials):
+        if not potentials:
+            raise ValueError('SumPotential needs at least one potential')
+        self.potentials = tuple(potentials)
+        for m in self.potentials:
+            if hasattr(m, 'locate'):
+                self.locate, self.has_fit = m.locate, getattr(m, 'has_fit', True)
+                break
+        for m in self.potentials:
+            if hasattr(m, 'describe'):
+                self.describe = m.describe
+                break
+
+    def __call__(self, x0, step):
+        total = self.potentials[0](x0, step)
+        for m in self.potentials[1:]:
+            total = total + m(x0, step)
+        return total

@@ -5,7 +5,8 @@
  * The reference has no FFI of its own: its seam is the Python
  * call `self.model.model(ts, timesteps, features)['z']` inside the reverse
  * loop.  Each entry point below names the reference code it replaces
- * (paths relative to the reference root).
+ * (paths relative to the reference root); genie_shape_potential, the
+ * shape potential of guided sampling, has no counterpart there and says so.
  *
  * Conventions
  *   - return 0 = ok, < 0 = error (GENIE_E_*); text via genie_last_error().
@@ -236,6 +237,51 @@ int genie_smc_reweight(genie_stream_t stream, int S, int K, int N, const float* 
                        float* log_w_acc /*[S K], in/out*/, float* x_out /*[S K,N,3]*/, int32_t* index_out /*[S K]*/,
                        float* ess_out /*[S]*/, int32_t* resampled_out /*[S]*/, void* work, size_t work_bytes);
 size_t genie_smc_reweight_work_bytes(int S, int K, int N);
+
+/* The shape potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle: a
+ * radius-of-gyration cap, a C-alpha clash term over all residue pairs and the caller's pairwise distance restraints
+ * (csrc/shape_kernels.hip; the reference has no counterpart, its one twisting function is the motif potential above).  For particle b
+ * with coordinates x_n (n = 0..N-1, Angstrom); all N rows are used (the twisted sampler's batches are never ragged):
+ *   centroid  m = mean_n x_n,  c_n = x_n - m,  rog = sqrt(sum_n |c_n|^2 / N)
+ *   E_rog   = rog_weight   * max(0, rog - rog_max)^2
+ *   E_clash = clash_weight * sum_{i<j, j-i >= clash_separation} max(0, clash_distance - d_ij)^2,   d_ij = |x_i - x_j|
+ *   E_rst   = sum_r w_r * ( max(0, lo_r - d_r)^2 + max(0, d_r - hi_r)^2 ),   d_r = |x_{i_r} - x_{j_r}|   (hi_r may be +inf, lo_r may be 0)
+ *   logp_out[b] = -(E_rog + E_clash + E_rst) / (2 var)
+ *   grad_out[b,n] = d logp[b] / d x_n
+ *                 = -(1/var) * [ rog_weight (rog - rog_max)_+ c_n / (N rog)
+ *                                - clash_weight sum_{j eligible} (clash_distance - d_nj)_+ u_nj
+ *                                + sum_{r containing n} w_r ((d_r - hi_r)_+ - (lo_r - d_r)_+) u_{n,partner} ],      u_nj = (x_n - x_j) / d_nj
+ * Where a distance, or rog, is exactly 0 in float32 its direction is 0: every output stays finite.  `var` is one float in device
+ * memory.  The likelihood is left unnormalised: every use in the sampler is a difference or a normalised weight.
+ * Restraints arrive as a per-residue table the host builds once (device memory): the entries of residue n are
+ * rst_offset[n] .. rst_offset[n+1] - 1 (rst_offset[0] = 0, rst_offset[N] = R2), entry k naming the partner rst_partner[k] and the
+ * restraint's lo, hi and weight.  Every restraint is listed at both of its residues (R2 = twice their number), partners ascending
+ * within a residue, so a residue's force is a gather in a fixed order; energies and counts are taken from the entries with
+ * partner > residue.  R2 = 0: no restraints, the five pointers may be NULL.  The caller validates the table; offsets and partners are
+ * clamped into range all the same.
+ * rog_weight == 0 or clash_weight == 0 switches that term off (energy and force).  report_out[b] holds GENIE_SHAPE_REPORT floats:
+ *   rog, min_distance, n_clash, e_rog, e_clash, e_restraint, n_violated, max_violation
+ * min_distance and n_clash (pairs with d < clash_distance) are always taken over the eligible pairs, whatever the weight, and
+ * min_distance is +inf when there is none; n_violated counts the restraints with d < lo or d > hi and max_violation is the largest
+ * such excess in Angstrom (0 when none); the three energies are the weighted E above, before the division by 2 var.  (Counts are
+ * stored as floats: exact up to 2^24.)
+ * logp_out and grad_out are given together or both NULL; report_out may be NULL; at least one output is asked for.
+ * Two launches on `stream`: grid (ceil(N / 64), B) work-groups that stage x0[b] in LDS (12 N bytes) and leave 8 partial values per
+ * tile in `work` (genie_shape_potential_work_bytes(B, N) = B * ceil(N / 64) * 32 bytes, 4-byte aligned), then one thread per
+ * particle that adds them in tile order.  No allocation, no synchronisation, no host read, no atomics: every output is written once
+ * in a fixed order, so two calls on the same inputs are bitwise equal.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 1; x0 or var NULL; no output asked for; logp_out and grad_out not given together; clash_separation < 1; a negative or
+ * non-finite rog_max, clash_distance, rog_weight or clash_weight; R2 < 0, R2 odd, or R2 > 0 with a NULL table; `work` NULL,
+ * misaligned or work_bytes too small; an N whose staging does not fit in LDS (160 KiB: N above 13 140). */
+#define GENIE_SHAPE_REPORT 8   /* rog, min_distance, n_clash, e_rog, e_clash, e_restraint, n_violated, max_violation */
+int genie_shape_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/,
+                          float rog_max, float rog_weight, float clash_distance, int clash_separation, float clash_weight,
+                          int R2, const int32_t* rst_offset /*[N+1]*/, const int32_t* rst_partner /*[R2]*/, const float* rst_lo,
+                          const float* rst_hi, const float* rst_weight /*[R2] each*/, const float* var /*[1], device*/,
+                          float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                          float* report_out /*[B,GENIE_SHAPE_REPORT] or NULL*/, void* work, size_t work_bytes);
+size_t genie_shape_potential_work_bytes(int B, int N);
 
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
