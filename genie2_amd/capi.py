@@ -112,10 +112,17 @@ SYMBOLS = {
     'genie_shape_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
                                          C.c_int] + [C.c_void_p] * 10 + [C.c_size_t]),
     'genie_shape_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'genie_secstruct_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_float] * 6 +
+                                  [C.c_void_p, C.c_float] + [C.c_void_p] * 5),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
 SHAPE_REPORT = ('rog', 'min_distance', 'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation')      # GENIE_SHAPE_REPORT slots
+
+SECSTRUCT_REPORT = ('helix_content', 'extended_content', 'n_helix', 'n_extended', 'e_helix', 'e_extended', 'e_target',
+                    'n_target_missed')      # GENIE_SECSTRUCT_REPORT slots
+# P-SEA's C-alpha criteria (Labesse et al. 1997) for d2, d3, d4 and chi from ideal coordinates: H mu, H sigma, E mu, E sigma
+SECSTRUCT_TABLE = (5.5, 5.3, 6.4, 0.77, 0.5, 0.5, 0.6, 0.25, 6.7, 9.9, 12.4, -0.12, 0.6, 0.9, 1.1, 0.45)
 
 _lib = None
 

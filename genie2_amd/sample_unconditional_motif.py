@@ -27,7 +27,12 @@ unconditional CLI: one length, `--write_start_rmsd`); it combines with `--align`
 `--rog_max`, `--clash_distance` and `--restraint_file` (with their weights, `--clash_separation` and `--shape_tausq`: the flags of
 genie2_amd/sample_unconditional_shape.py) add shape guidance: the potential is then SumPotential(MotifPotential, ShapePotential), and
 `--write_shape_report` writes outdir/shape/{length}_{index}.txt as that CLI does.  Lengths too short for a restrained residue are
-skipped."""
+skipped.
+
+`--helix_min` / `--helix_max`, `--extended_min` / `--extended_max` and `--ss_target` (with their weights and `--ss_tausq`: the flags
+of add_secstruct_arguments in the same module) add secondary-structure guidance: the potentials asked for are summed in the order
+motif, shape, secondary structure, `--write_secstruct` writes outdir/secstruct/{length}_{index}.txt as that CLI does, and lengths
+other than the blueprint's are skipped."""
 import os
 
 from tqdm import tqdm
@@ -35,8 +40,9 @@ from tqdm import tqdm
 from .diffusion import load_pretrained_model
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, write_start_rmsd
-from .sample_unconditional_shape import (add_shape_arguments, restrained_lengths, shape_constants, shape_potential,
-                                         write_shape_report)
+from .sample_unconditional_shape import (add_secstruct_arguments, add_shape_arguments, report_fields, restrained_lengths,
+                                         secstruct_constants, secstruct_potential, shape_constants, shape_potential, sum_potentials,
+                                         target_lengths, write_secstruct_report, write_shape_report)
 
 
 def load_motif_segments(filepath):
@@ -87,7 +93,7 @@ class MotifRunner(UnconditionalRunner):
         if short:
             print('skipping lengths shorter than the {}-residue motif: {}'.format(total, ', '.join(map(str, short))))
         tasks = [t for t in tasks if t['length'] >= total]
-        return restrained_lengths(tasks, shape_constants(params)['restraints'])
+        return target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
 
     def create_constants(self, params):
         c = super().create_constants(params)
@@ -99,16 +105,18 @@ class MotifRunner(UnconditionalRunner):
         c['groups'] = load_motif_groups(params['motif_file']) if c['motif_groups'] == 'file' else None
         c['num_particles'] = params.get('num_particles')
         c.update(shape_constants(params))
+        c.update(secstruct_constants(params))
         return c
 
     def execute(self, constants, tasks, device):
-        from . import pack
-        from .smc import MotifPotential, SumPotential, TwistedSampler
+        from . import capi, pack
+        from .smc import MotifPotential, TwistedSampler
         model = load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
         sampler = TwistedSampler(model)
         abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
         for task in tqdm(tasks, desc=device):
             shape = shape_potential(constants, task['length'], abar, device)
+            secstruct = secstruct_potential(constants, task['length'], abar, device)
             remaining = constants['num_samples']
             while remaining > 0:
                 batch = min(constants['batch_size'], remaining)
@@ -122,8 +130,7 @@ class MotifRunner(UnconditionalRunner):
                 potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
                                            max_offsets=constants['max_offsets'], device=device, align=constants['align'],
                                            groups=constants.get('groups'))
-                if shape is not None:
-                    potential = SumPotential(potential, shape)
+                potential = sum_potentials(potential, shape, secstruct)
                 # (with --num_particles: `batch` systems, each returning its best particle)
                 systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'],
                                                                              'return_particles': 'best'}
@@ -139,7 +146,11 @@ class MotifRunner(UnconditionalRunner):
                 if constants['write_motif_locations']:
                     write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
                 if constants['write_shape_report'] and shape is not None:
-                    write_shape_report(sampler.last_shape, os.path.join(constants['outdir'], 'shape'), task['length'], offset)
+                    write_shape_report(report_fields(sampler.last_shape, capi.SHAPE_REPORT), os.path.join(constants['outdir'], 'shape'),
+                                       task['length'], offset)
+                if constants['write_secstruct'] and secstruct is not None:
+                    write_secstruct_report(sampler.last_secstruct, report_fields(sampler.last_shape, capi.SECSTRUCT_REPORT),
+                                           os.path.join(constants['outdir'], 'secstruct'), task['length'], offset)
                 remaining -= batch
 
 
@@ -185,6 +196,7 @@ def build_parser():
                         'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
                         'written (an addition to the reference CLI, like --align)')
     add_shape_arguments(p)
+    add_secstruct_arguments(p)
     return p
 
 

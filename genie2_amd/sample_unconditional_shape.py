@@ -2,7 +2,7 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three is needed.
+least one of the three, or a secondary-structure term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -10,9 +10,17 @@ Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A 
 `--write_shape_report` adds outdir/shape/{length}_{index}.txt beside each PDB, one `key value` line per report field of the written
 structure: rog, min_distance, n_clash, e_rog, e_clash, e_restraint, n_violated, max_violation (ShapePotential.describe).
 
+`--helix_min` / `--helix_max` and `--extended_min` / `--extended_max` keep the soft helix / extended content (fractions of the
+length - 4 five-residue windows) in a range, and `--ss_target STRING|FILE` pulls residues to a blueprint over `H`, `E` and `-` (or `C`:
+free; in a file whitespace is ignored and `#` starts a comment): a SecStructPotential (csrc/secstruct_kernels.hip), summed with the
+shape terms when both are asked for and enough on its own.  Giving only one of min / max leaves the other at 0 / 1.  "Extended" is
+local geometry only, with no strand pairing.  A length other than the blueprint's is skipped.  `--write_secstruct` adds
+outdir/secstruct/{length}_{index}.txt: the hard assignment of the written structure as a string over `HEC`, then one `key value` line
+per field of SecStructPotential.describe.
+
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
-add_shape_arguments too and then guides with the sum of both potentials."""
+add_shape_arguments and add_secstruct_arguments too and then guides with the sum of the potentials asked for."""
 import os
 
 from tqdm import tqdm
@@ -21,6 +29,8 @@ from .sample_unconditional import PartialParser, UnconditionalRunner, write_star
 
 SHAPE_KEYS = ('rog_max', 'rog_weight', 'clash_distance', 'clash_separation', 'clash_weight', 'shape_tausq')
 COUNTS = ('n_clash', 'n_violated')
+SECSTRUCT_KEYS = ('helix_weight', 'extended_weight', 'ss_target_weight', 'ss_tausq')
+SECSTRUCT_COUNTS = ('n_helix', 'n_extended', 'n_target_missed')
 
 
 def add_shape_arguments(parser):
@@ -86,29 +96,117 @@ def write_shape_report(last_shape, directory, length, offset):
                 fh.write(('{} {:d}\n' if key in COUNTS else '{} {:.3f}\n').format(key, column[i].item()))
 
 
+def add_secstruct_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    for name, word in (('helix', 'helix'), ('extended', 'extended (strand-like, local geometry only)')):
+        parser.add_argument('--%s_min' % name, type=float, default=None,
+                            help='Guide the soft %s content, a fraction of the five-residue windows, above this; default: no such '
+                                 'bound' % word + tail)
+        parser.add_argument('--%s_max' % name, type=float, default=None,
+                            help='Guide the soft %s content below this fraction; default: no such bound' % word + tail)
+        parser.add_argument('--%s_weight' % name, type=float, default=1.0, help='Weight of the %s content term' % name + tail)
+    parser.add_argument('--ss_target', type=str, default=None,
+                        help='Blueprint over H, E and - (or C: free), one character per residue, or a file that holds it' + tail)
+    parser.add_argument('--ss_target_weight', type=float, default=1.0, help='Weight of the blueprint term' + tail)
+    parser.add_argument('--ss_tausq', type=float, default=1.0,
+                        help='Likelihood variance tau^2 of the secondary-structure terms, Angstrom^2' + tail)
+    parser.add_argument('--write_secstruct', action='store_true',
+                        help='Write outdir/secstruct/{length}_{index}.txt: the H / E / C assignment, soft contents, counts and energies '
+                             'of every written structure' + tail)
+
+
+def secstruct_constants(params):
+    """The secondary-structure keys of a runner's constants: the flags of add_secstruct_arguments, each min / max pair as 'helix' /
+    'extended' = (min, max) or None (one of the two given: the other is 0 / 1), the blueprint read into 'ss_target'."""
+    from .smc import load_ss_target
+    defaults = dict(helix_weight=1.0, extended_weight=1.0, ss_target_weight=1.0, ss_tausq=1.0)
+    c = {k: params.get(k, defaults[k]) for k in SECSTRUCT_KEYS}
+    for name in ('helix', 'extended'):
+        lo, hi = params.get(name + '_min'), params.get(name + '_max')
+        c[name] = None if lo is None and hi is None else (0.0 if lo is None else lo, 1.0 if hi is None else hi)
+    c['ss_target'] = load_ss_target(params['ss_target']) if params.get('ss_target') else None
+    c['write_secstruct'] = bool(params.get('write_secstruct', False))
+    return c
+
+
+def has_secstruct_terms(constants):
+    return constants.get('helix') is not None or constants.get('extended') is not None or constants.get('ss_target') is not None
+
+
+def target_lengths(tasks, ss_target):
+    """The tasks of the blueprint's length; the others are skipped with one printed line."""
+    if ss_target is None:
+        return tasks
+    other = [t['length'] for t in tasks if t['length'] != len(ss_target)]
+    if other:
+        print('skipping lengths other than the {} residues of the blueprint: {}'.format(len(ss_target), ', '.join(map(str, other))))
+    return [t for t in tasks if t['length'] == len(ss_target)]
+
+
+def secstruct_potential(constants, length, abar, device):
+    """The SecStructPotential the constants ask for at this length, or None when they ask for no term.  (Lengths other than the
+    blueprint's never get here: target_lengths drops them when the tasks are made.)"""
+    if not has_secstruct_terms(constants):
+        return None
+    from .smc import SecStructPotential
+    return SecStructPotential(length, abar, helix=constants['helix'], helix_weight=constants['helix_weight'],
+                              extended=constants['extended'], extended_weight=constants['extended_weight'],
+                              target=constants['ss_target'], target_weight=constants['ss_target_weight'],
+                              tausq=constants['ss_tausq'], device=device)
+
+
+def sum_potentials(*potentials):
+    """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
+    from .smc import SumPotential
+    members = [p for p in potentials if p is not None]
+    return None if not members else members[0] if len(members) == 1 else SumPotential(*members)
+
+
+def report_fields(report, names):
+    """The fields `names` of a sampler's merged report, in that order."""
+    return {k: report[k] for k in names}
+
+
+def write_secstruct_report(assignment, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: the assignment of TwistedSampler.last_secstruct as a string over
+    HEC, then a `key value` line per field of `report` (the secondary-structure fields of last_shape), %.3f for contents and
+    energies, %d for counts."""
+    from .smc import ss_string
+    os.makedirs(directory, exist_ok=True)
+    for i, row in enumerate(assignment.tolist()):
+        with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
+            fh.write(ss_string(row) + '\n')
+            for key, column in report.items():
+                fh.write(('{} {:d}\n' if key in SECSTRUCT_COUNTS else '{} {:.3f}\n').format(key, column[i].item()))
+
+
 class ShapeRunner(UnconditionalRunner):
     def create_tasks(self, params):
         from .smc import load_restraints
         restraints = load_restraints(params['restraint_file']) if params.get('restraint_file') else []
-        return restrained_lengths(super().create_tasks(params), restraints)
+        return target_lengths(restrained_lengths(super().create_tasks(params), restraints), secstruct_constants(params)['ss_target'])
 
     def create_constants(self, params):
         c = super().create_constants(params)
         c.update({k: params[k] for k in ('guidance_alpha', 'ess_threshold', 'last_unguided_steps')})
         c['num_particles'] = params.get('num_particles')
         c.update(shape_constants(params))
-        if not has_shape_terms(c):
-            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file')
+        c.update(secstruct_constants(params))
+        if not has_shape_terms(c) and not has_secstruct_terms(c):
+            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, or a secondary-structure '
+                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target)')
         return c
 
     def execute(self, constants, tasks, device):
-        from . import pack
+        from . import capi, pack
         from .smc import TwistedSampler
         model = self.load_model(constants, device)
         sampler = TwistedSampler(model)
         abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
         for task in tqdm(tasks, desc=device):
-            potential = shape_potential(constants, task['length'], abar, device)
+            shape = shape_potential(constants, task['length'], abar, device)
+            secstruct = secstruct_potential(constants, task['length'], abar, device)
+            potential = sum_potentials(shape, secstruct)
             remaining = constants['num_samples']
             while remaining > 0:
                 batch = min(constants['batch_size'], remaining)
@@ -130,8 +228,12 @@ class ShapeRunner(UnconditionalRunner):
                 if constants.get('write_start_rmsd'):
                     write_start_rmsd(sampler.last_start_rmsd, os.path.join(constants['outdir'], 'start_rmsd'),
                                      ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
-                if constants['write_shape_report']:
-                    write_shape_report(sampler.last_shape, os.path.join(constants['outdir'], 'shape'), task['length'], offset)
+                if constants['write_shape_report'] and shape is not None:
+                    write_shape_report(report_fields(sampler.last_shape, capi.SHAPE_REPORT), os.path.join(constants['outdir'], 'shape'),
+                                       task['length'], offset)
+                if constants['write_secstruct'] and secstruct is not None:
+                    write_secstruct_report(sampler.last_secstruct, report_fields(sampler.last_shape, capi.SECSTRUCT_REPORT),
+                                           os.path.join(constants['outdir'], 'secstruct'), task['length'], offset)
                 remaining -= batch
 
 
@@ -161,6 +263,7 @@ def build_parser():
                         'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
                         'written')
     add_shape_arguments(p)
+    add_secstruct_arguments(p)
     return p
 
 

@@ -4,7 +4,9 @@ function, :465-576 the loop) without its wandb / file logging.  The gradient tor
 Denoiser is `GenieEngine.denoise_vjp` here (HIP backward kernels, frames held fixed exactly as `T(rots.detach(), trans.detach())`
 does); the reference's potential acts on a [B, N, 3] tensor and stays in PyTorch here (motif_twisting_function), with
 MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).  ShapePotential (csrc/shape_kernels.hip: radius of
-gyration, clashes, distance restraints; not in the reference) is the second built-in potential and SumPotential adds potentials.
+gyration, clashes, distance restraints; not in the reference) is the second built-in potential, SecStructPotential
+(csrc/secstruct_kernels.hip: helix / extended content and a blueprint; the reference's sampler/secstruct.py runs P-SEA on the host and
+is not differentiable) the third, and SumPotential adds potentials.
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -126,8 +128,10 @@ class TwistedSampler(UnconditionalSampler):
     After _sample, `last_fit` holds what the twisting function's `locate` says of the final coordinates (MotifPotential.locate: 'best',
     'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample; with motif groups also 'group_rmsd' and the 'groups' labels),
     or None when it has no `locate`; `last_shape` what its `describe` says of them (ShapePotential.describe: 'rog', 'min_distance',
-    'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation' as CPU tensors, one row per returned sample), or None
-    when it has no `describe`.
+    'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation' as CPU tensors, one row per returned sample; with a
+    SecStructPotential its eight fields, and with a SumPotential every member's), or None when it has no `describe`; `last_secstruct`
+    what its `assign` says of them (SecStructPotential.assign: int8 [rows, N] on the CPU, 0 C, 1 H, 2 E), or None when it has no
+    `assign`.
     Optional 'num_steps' = K (not in the reference) visits the K timesteps of pack.respaced_steps with the ancestral kernel between
     them (pack.twisted_coefficients): `ess_trace` then has K - 1 entries, the last visited step takes the role of step 1, and
     `last_unguided_steps` and the potential keep reading the timestep itself.  'sampler': 'ddim' is refused (ValueError): the
@@ -248,6 +252,7 @@ class TwistedSampler(UnconditionalSampler):
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans.detach()).items()}
         self.last_shape = {k: v.cpu() for k, v in twist.describe(trans.detach()).items()} if hasattr(twist, 'describe') else None
+        self.last_secstruct = twist.assign(trans.detach()).cpu() if hasattr(twist, 'assign') else None
         feats['atom_positions'] = trans.detach().cpu()
         self.last_start_rmsd = None if partial is None else start_rmsd(feats['atom_positions'], partial[1], feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
@@ -357,6 +362,7 @@ class TwistedSampler(UnconditionalSampler):
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans).items()}
         self.last_shape = {k: v.cpu() for k, v in twist.describe(trans).items()} if hasattr(twist, 'describe') else None
+        self.last_secstruct = twist.assign(trans).cpu() if hasattr(twist, 'assign') else None
         feats['atom_positions'] = trans.cpu()
         self.last_start_rmsd = None if start is None else start_rmsd(feats['atom_positions'], start, feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
@@ -795,10 +801,187 @@ class ShapePotential:
         return tuple(t for t in outs if t is not None)
 
 
+SS_CODES = {'-': 0, 'H': 1, 'E': 2}      # the int8 codes of genie_secstruct_potential's target
+SS_LETTERS = 'CHE'                        # its assignment codes 0, 1, 2 as letters
+
+
+def load_ss_target(path_or_string):
+    """A secondary-structure blueprint for SecStructPotential, as a string over `HE-`: `H` helix, `E` extended, `-` or `C` free.
+    The argument is the blueprint itself or the path of a file that holds it; in a file whitespace (line breaks included) is
+    ignored and `#` starts a comment.  Anything else raises ValueError."""
+    import os
+    text, where = str(path_or_string), 'the blueprint'
+    if os.path.isfile(text):
+        where = text
+        with open(text) as fh:
+            text = ''.join(''.join(line.split('#', 1)[0].split()) for line in fh)
+    else:
+        text = ''.join(text.split())
+    bad = sorted(set(text) - set('HEC-'))
+    if bad:
+        raise ValueError('%s: expected H, E and - (or C) only, got %r' % (where, ''.join(bad)))
+    if not text:
+        raise ValueError('%s is empty' % where)
+    return text.replace('C', '-')
+
+
+def ss_target_windows(target):
+    """The number of five-residue windows a blueprint string targets: those whose residues are all H or all E."""
+    return sum(1 for i in range(len(target) - 4) if target[i] in 'HE' and target[i:i + 5] == target[i] * 5)
+
+
+def ss_string(codes):
+    """A row of assignment codes (0 C, 1 H, 2 E) as a string over `HEC`."""
+    return ''.join(SS_LETTERS[int(c)] for c in codes)
+
+
+class _SecStructPotentialFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, pot, var):
+        logp, grad = pot._launch(pot._checked(x0), var)
+        ctx.save_for_backward(grad)
+        return logp
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        grad, = ctx.saved_tensors
+        return grad_output[:, None, None] * grad, None, None
+
+
+class SecStructPotential:
+    """Secondary-structure guidance as one HIP pass (genie_secstruct_potential, csrc/secstruct_kernels.hip; include/genie_hip.h
+    states the mathematics): `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for
+    TwistedSampler beside MotifPotential and ShapePotential (SumPotential adds them).  Every five-residue window is scored against a
+    helix and an extended class on its C-alpha distances i..i+2, i..i+3, i..i+4 and a chirality, with a rational score in (0, 1];
+    the soft count of a class is the sum of its scores.  Three terms:
+      helix     (min, max), fractions of the N - 4 windows: the soft helix count is kept between them by a squared hinge (None: off),
+                weighted helix_weight;
+      extended  the same for the extended class, weighted extended_weight;
+      target    a blueprint string over `HE-` of length n_res (load_ss_target reads one): every window whose five residues are all
+                H, or all E, is pulled to that class harmonically, weighted target_weight.
+    log p = -(E_helix + E_extended + E_target) / (2 var), var = xstart_variance(alphas_cumprod[step], tausq) computed on the device,
+    so nothing on the per-step path reads device memory from the host; the forward keeps the gradient the kernel computes and the
+    backward scales it.  The likelihood is unnormalised.  `table` replaces the 16 class constants (capi.SECSTRUCT_TABLE: H mu, H
+    sigma, E mu, E sigma over d2, d3, d4, chi).
+
+    Everything is validated on the host before the device is looked at; a potential with no term enabled is a ValueError.
+    `describe(x)` reports every sample of x: 'helix_content', 'extended_content' (soft count / windows), 'n_helix', 'n_extended'
+    (residues of the hard assignment, int64), 'e_helix', 'e_extended', 'e_target' (the weighted energies, before the division by
+    2 var), 'n_target_missed' (blueprint residues whose hard assignment differs, int64), [B] tensors on the potential's device;
+    `assign(x)` is the hard assignment, int8 [B, N] with 0 C, 1 H, 2 E.
+
+    "Extended" is local geometry only: there is no strand pairing (P-SEA's inter-strand criteria are out of scope), so it says that a
+    stretch is straight and flat like a strand, not that it sits in a sheet.  The defaults (the table, weights 1, tausq = 1 A^2, the
+    rational score) are design choices: no trained checkpoint is in the tree, so their effect on sample quality is unmeasured."""
+
+    def __init__(self, n_res, alphas_cumprod, helix=None, helix_weight=1.0, extended=None, extended_weight=1.0, target=None,
+                 target_weight=1.0, table=None, tausq=1.0, device='cuda'):
+        import ctypes as C
+        import math
+        from . import capi
+        self.n_res = int(n_res)
+        if self.n_res < 5:
+            raise ValueError('n_res must be at least 5 (a window covers five residues), got %r' % (n_res,))
+        if helix is None and extended is None and target is None:
+            raise ValueError('no term enabled: give helix, extended or target')
+        for name, v in (('helix_weight', helix_weight), ('extended_weight', extended_weight), ('target_weight', target_weight)):
+            if not (math.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, v))
+        bounds = {}
+        for name, v in (('helix', helix), ('extended', extended)):
+            if v is None:
+                bounds[name] = None
+                continue
+            try:
+                lo, hi = (float(e) for e in v)
+            except (TypeError, ValueError):
+                raise ValueError('%s must be (min, max), got %r' % (name, v)) from None
+            if not 0.0 <= lo <= hi <= 1.0:
+                raise ValueError('%s needs 0 <= min <= max <= 1, got %r' % (name, v))
+            bounds[name] = (lo, hi)
+        if not (math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        table = capi.SECSTRUCT_TABLE if table is None else tuple(float(v) for v in (table.reshape(-1).tolist() if torch.is_tensor(table) else table))
+        if len(table) != 16 or not all(math.isfinite(v) for v in table):
+            raise ValueError('table must hold 16 finite numbers (H mu, H sigma, E mu, E sigma over d2, d3, d4, chi), got %r' % (table,))
+        if min(table[4:8] + table[12:16]) <= 0:
+            raise ValueError('every sigma of the table must be > 0, got %r' % (table[4:8] + table[12:16],))
+        if target is not None:
+            if not isinstance(target, str):
+                raise ValueError('target must be a string over H, E and -, got %r' % (target,))
+            if len(target) != self.n_res:
+                raise ValueError('the target names %d residues, the potential has %d' % (len(target), self.n_res))
+            if set(target) - set(SS_CODES):
+                raise ValueError('target must hold H, E and - only, got %r' % ''.join(sorted(set(target) - set(SS_CODES))))
+            if ss_target_windows(target) == 0:
+                raise ValueError('the target has no run of five equal H or E residues: it targets no window')
+        # a term that is off is a weight of 0 to the entry
+        self.helix, self.helix_weight = ((0.0, 1.0), 0.0) if bounds['helix'] is None else (bounds['helix'], float(helix_weight))
+        self.extended, self.extended_weight = ((0.0, 1.0), 0.0) if bounds['extended'] is None else (bounds['extended'], float(extended_weight))
+        self.target, self.target_weight = target, (0.0 if target is None else float(target_weight))
+        self.table, self.tausq = table, float(tausq)
+        self._table = (C.c_float * 16)(*table)
+        self.lib = capi.load_library()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise capi.GenieError('SecStructPotential runs on the GPU (libgenie_hip); there is no CPU path')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.target_t = None if target is None else torch.tensor([SS_CODES[c] for c in target], dtype=torch.int8).to(self.device)
+        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+
+    def variance(self, step):
+        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
+
+    def __call__(self, x0, step):
+        return _SecStructPotentialFn.apply(x0, self, self.variance(step))
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        from . import capi
+        report, _ = self._launch(self._checked(x), self._one, report=True)                 # (the energies do not depend on var)
+        counts = ('n_helix', 'n_extended', 'n_target_missed')
+        return {k: report[:, i].round().long() if k in counts else report[:, i].clone() for i, k in enumerate(capi.SECSTRUCT_REPORT)}
+
+    def assign(self, x):
+        """The hard assignment of every sample of x [B,N,3]: int8 [B, N], 0 C, 1 H, 2 E, on the potential's device."""
+        return self._launch(self._checked(x), self._one, report=True)[1]
+
+    def _checked(self, x0):
+        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
+            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
+        if x0.device != self.device:
+            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
+        return x0.detach().to(torch.float32).contiguous()
+
+    def _launch(self, x, var, report=False):
+        """One call of the C entry on x (f32, contiguous): (report [B, 8], assignment [B, N]) when `report`, else (logp, grad)."""
+        import ctypes as C
+        from . import capi
+        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        if report:
+            outs = [None, None, torch.empty(B, len(capi.SECSTRUCT_REPORT), **f32), torch.empty(B, self.n_res, dtype=torch.int8, device=x.device)]
+        else:
+            outs = [torch.empty(B, **f32), torch.empty_like(x), None, None]
+        with torch.cuda.device(x.device):
+            rc = self.lib.genie_secstruct_potential(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
+                                                    self._table, self.helix[0], self.helix[1], self.helix_weight, self.extended[0],
+                                                    self.extended[1], self.extended_weight, p(self.target_t), self.target_weight,
+                                                    p(var), *(p(t) for t in outs))
+        if rc != 0:
+            msg = self.lib.genie_last_error(None)
+            raise capi.GenieError('genie_secstruct_potential failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        return tuple(t for t in outs if t is not None)
+
+
 class SumPotential:
     """The sum of twisting functions: `SumPotential(a, b, ...)(x0, step) = a(x0, step) + b(x0, step) + ...`, added in that order.
-    `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential), `describe` that of the first member
-    that has one (ShapePotential); an attribute no member has is absent, so TwistedSampler's hasattr checks see through the sum."""
+    `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential); `describe` is the merge of the reports
+    of every member that has one (ShapePotential, SecStructPotential), in member order, the first member winning on a key two of them
+    report; `assign` is that of the first member that has one (SecStructPotential).  An attribute no member has is absent, so
+    TwistedSampler's hasattr checks see through the sum."""
 
     def __init__(self, *potentials):
         if not potentials:
@@ -808,10 +991,20 @@ class SumPotential:
             if hasattr(m, 'locate'):
                 self.locate, self.has_fit = m.locate, getattr(m, 'has_fit', True)
                 break
+        if any(hasattr(m, 'describe') for m in self.potentials):
+            self.describe = self._describe
+        for m in self.potentials:
+            if hasattr(m, 'assign'):
+                self.assign = m.assign
+                break
+
+    def _describe(self, x):
+        out = {}
         for m in self.potentials:
             if hasattr(m, 'describe'):
-                self.describe = m.describe
-                break
+                for k, v in m.describe(x).items():
+                    out.setdefault(k, v)
+        return out
 
     def __call__(self, x0, step):
         total = self.potentials[0](x0, step)

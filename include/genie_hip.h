@@ -6,7 +6,8 @@
  * call `self.model.model(ts, timesteps, features)['z']` inside the reverse
  * loop.  Each entry point below names the reference code it replaces
  * (paths relative to the reference root); genie_shape_potential, the
- * shape potential of guided sampling, has no counterpart there and says so.
+ * shape potential of guided sampling, has no counterpart there and says so,
+ * and genie_secstruct_potential has no differentiable one.
  *
  * Conventions
  *   - return 0 = ok, < 0 = error (GENIE_E_*); text via genie_last_error().
@@ -282,6 +283,54 @@ int genie_shape_potential(genie_stream_t stream, int B, int N, const float* x0 /
                           float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
                           float* report_out /*[B,GENIE_SHAPE_REPORT] or NULL*/, void* work, size_t work_bytes);
 size_t genie_shape_potential_work_bytes(int B, int N);
+
+/* The secondary-structure potential of twisted-diffusion / SMC sampling with its gradient, a per-particle report and a hard
+ * assignment, without a handle: soft bounds on the helix and the extended content and an optional per-residue blueprint, scored on
+ * C-alpha geometry alone (csrc/secstruct_kernels.hip).  The reference has no differentiable counterpart: the example statistic of
+ * genie/sampler/secstruct.py ("more than 50 % alpha-helix") writes a PDB and runs biotite's P-SEA assignment on the host.  For
+ * particle b with coordinates x_n (n = 0..N-1, Angstrom; all N rows are used) there are W = N - 4 windows, window i covering
+ * residues i..i+4, with four features
+ *   d2 = |x_{i+2} - x_i|,  d3 = |x_{i+3} - x_i|,  d4 = |x_{i+4} - x_i|,
+ *   chi = ((b1 x b2) . b3) / (|b1| |b2| |b3|),   b_k = x_{i+k} - x_{i+k-1}, k = 1..3
+ * (chi is smooth, lies in [-1, 1] and changes sign under mirroring, which distances cannot).  For class c in {H (helix), E
+ * (extended)} `table` holds four targets mu and four tolerances sigma, 16 host floats copied by value: H mu[4], H sigma[4], E mu[4],
+ * E sigma[4], each in the order d2, d3, d4, chi.  Per window
+ *   z_cf = (f - mu_cf) / sigma_cf,   u_c,i = 1/4 sum_f z_cf^2,   s_c,i = 1 / (1 + u_c,i)
+ * (a rational score: its gradient decays polynomially, so a coil far from any target is still guided, and it needs no exp), and
+ * with the soft window count n_c = sum_i s_c,i
+ *   E_c   = c_weight * [ max(0, W c_min - n_c)^2 + max(0, n_c - W c_max)^2 ]      c = helix, extended; the bounds are fractions
+ *   E_tgt = target_weight * sum_{i targeted as c} u_c,i
+ *   logp_out[b] = -(E_H + E_E + E_tgt) / (2 var)
+ *   grad_out[b,n] = d logp[b] / d x_n, analytic, with d s / d x = -s^2 d u / d x
+ * Counts, not fractions, enter the hinge, so the force per window does not shrink with N.  `target` is N int8 codes in device
+ * memory, 0 free, 1 H, 2 E (any other value counts as 0), or NULL: window i is targeted as c when target[i..i+4] all equal c.
+ * A distance that is exactly 0 in float32 has direction 0, and a window with any |b_k| = 0 has chi = 0 and no chi force: every
+ * output is finite for finite inputs.  A weight of 0 switches its term off (energy and force).  `var` is one float in device memory;
+ * the likelihood is left unnormalised.
+ * Hard assignment (for reporting, not differentiated): window i is class c when all four |z_cf| <= 1; residue n is H if any window
+ * containing it is H, otherwise E if any is E, otherwise C.  assign_out[b,n] is 0 C, 1 H, 2 E.  "Extended" is local geometry only:
+ * there is no strand pairing.  report_out[b] holds GENIE_SECSTRUCT_REPORT floats:
+ *   helix_content (n_H / W), extended_content (n_E / W), n_helix, n_extended (residues of the hard assignment), e_helix, e_extended,
+ *   e_target (the weighted E above, before the division by 2 var), n_target_missed (residues with target H or E whose hard
+ *   assignment differs; 0 with a NULL target)
+ * (counts are stored as floats: exact up to 2^24).  logp_out and grad_out are given together or both NULL; report_out and assign_out
+ * may be NULL; at least one output is asked for.
+ * One launch on `stream`: one work-group of 256 threads per particle stages x0[b] and its windows in LDS (32 N bytes), reduces in a
+ * fixed tree and computes the gradient as a gather over the at most five windows of a residue.  No allocation, no synchronisation,
+ * no host read, no atomics, no work buffer: every output is written once in a fixed order, so two calls on the same inputs are
+ * bitwise equal.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 5; x0, var or table NULL; no output asked for; logp_out and grad_out not given together; a sigma that is <= 0 or not
+ * finite (or a mu that is not finite); a negative or non-finite weight; a bound outside [0, 1] or min > max; target_weight > 0 with
+ * a NULL target; an N whose staging does not fit in LDS (160 KiB: N above 5 122). */
+#define GENIE_SECSTRUCT_REPORT 8   /* helix_content, extended_content, n_helix, n_extended, e_helix, e_extended, e_target, n_target_missed */
+int genie_secstruct_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/,
+                              const float* table /*16 host floats: H mu[4], H sigma[4], E mu[4], E sigma[4]*/,
+                              float helix_min, float helix_max, float helix_weight,
+                              float extended_min, float extended_max, float extended_weight,
+                              const int8_t* target /*[N] device, or NULL*/, float target_weight,
+                              const float* var /*[1], device*/, float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                              float* report_out /*[B,GENIE_SECSTRUCT_REPORT] or NULL*/, int8_t* assign_out /*[B,N] or NULL; 0 C, 1 H, 2 E*/);
 
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
