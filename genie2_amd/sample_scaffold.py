@@ -14,7 +14,7 @@ from tqdm import tqdm
 
 from .diffusion import load_pretrained_model
 from .multiprocessor import MultiProcessor
-from .sample_unconditional import PartialParser, check_start_step_flag, write_start_rmsd
+from .sample_unconditional import PartialParser, UnconditionalRunner, check_start_step_flag, write_start_rmsd
 from .sampler import ScaffoldSampler
 
 
@@ -63,11 +63,8 @@ class ScaffoldRunner(MultiProcessor):
         sampler = ScaffoldSampler(self.load_model(constants, device))
         for task in tqdm(tasks, desc=device):
             outdir = os.path.join(constants['outdir'], 'motif={}'.format(task['motif_name']))
-            remaining = constants['num_samples']
-            while remaining > 0:
-                batch = min(constants['batch_size'], remaining)
-                offset = constants['num_samples'] - remaining
-                prefix = task.get('design', task['motif_name'])
+            prefix = task.get('design', task['motif_name'])
+            for batch, offset in UnconditionalRunner.batches(constants, outdir, prefix):      # (no --resume here: every batch)
                 partial = {} if 'design' not in task else {'design_filepath': task['design_filepath'], 'motif_filepath': task['motif_filepath'],
                                                            'start_step': constants['start_step']}
                 sampler.sample({
@@ -78,7 +75,6 @@ class ScaffoldRunner(MultiProcessor):
                 if partial and constants.get('write_start_rmsd'):
                     write_start_rmsd(sampler.last_start_rmsd, os.path.join(outdir, 'start_rmsd'),
                                      ['{}_{}'.format(prefix, offset + i) for i in range(batch)])
-                remaining -= batch
 
 
 def build_parser():

@@ -100,32 +100,36 @@ class UnconditionalRunner(MultiProcessor):
     def load_model(self, constants, device):
         return load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
 
+    @staticmethod
+    def batches(constants, outdir, prefix):
+        """(batch, offset) of every sampler call that constants['num_samples'] in batches of constants['batch_size'] need; with
+        constants['resume'] without the batches whose outdir/pdbs/{prefix}_{offset + i}.pdb all exist (written by an earlier,
+        interrupted run)."""
+        remaining = constants['num_samples']
+        while remaining > 0:
+            batch = min(constants['batch_size'], remaining)
+            offset = constants['num_samples'] - remaining
+            remaining -= batch
+            if not (constants.get('resume') and all(os.path.exists(os.path.join(outdir, 'pdbs', '{}_{}.pdb'.format(prefix, offset + i)))
+                                                    for i in range(batch))):
+                yield batch, offset
+
     def execute(self, constants, tasks, device):
         sampler = UnconditionalSampler(self.load_model(constants, device))
         for task in tqdm(tasks, desc=device):
-            remaining = constants['num_samples']
-            while remaining > 0:
-                batch = min(constants['batch_size'], remaining)
-                offset = constants['num_samples'] - remaining
-                if constants.get('resume') and all(
-                        os.path.exists(os.path.join(constants['outdir'], 'pdbs', '{}_{}.pdb'.format(task['length'], offset + i)))
-                        for i in range(batch)):
-                    remaining -= batch           # this batch was written by an earlier (interrupted) run
-                    continue
+            for batch, offset in self.batches(constants, constants['outdir'], task['length']):
                 sampler.sample({
                     'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
-                    'outdir': constants['outdir'], 'prefix': str(task['length']),
-                    'offset': constants['num_samples'] - remaining,
+                    'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
                     'num_steps': constants.get('num_steps'), 'sampler': constants.get('sampler'), 'eta': constants.get('eta'),
                     **self.partial_params(constants)})
                 if constants.get('write_start_rmsd'):
                     write_start_rmsd(sampler.last_start_rmsd, os.path.join(constants['outdir'], 'start_rmsd'),
                                      ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
-                remaining -= batch
 
 
-def build_parser():
-    p = PartialParser('input_pdb', 'Structure file whose C-alpha backbone every sample starts from')
+def add_common_arguments(p):
+    """The model, output and length flags every sampling CLI of the package shares."""
     p.add_argument('--name', type=str, help='Model name', required=True)
     p.add_argument('--epoch', type=int, help='Model epoch', required=True)
     p.add_argument('--rootdir', type=str, help='Root directory', default='results')
@@ -138,6 +142,11 @@ def build_parser():
     p.add_argument('--length_step', type=int, help='Length step size', default=1)
     p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
     p.add_argument('--sequential_order', action='store_true', help='Run in increasing order of length')
+
+
+def build_parser():
+    p = PartialParser('input_pdb', 'Structure file whose C-alpha backbone every sample starts from')
+    add_common_arguments(p)
     p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist (not in the reference CLI)')
     p.add_argument('--num_steps', type=int, default=None,
                    help='Run the reverse process on this many of the n_timestep steps; default: all (not in the reference CLI)')

@@ -35,14 +35,9 @@ motif, shape, secondary structure, `--write_secstruct` writes outdir/secstruct/{
 other than the blueprint's are skipped."""
 import os
 
-from tqdm import tqdm
-
-from .diffusion import load_pretrained_model
 from .motif import load_motif_spec
-from .sample_unconditional import PartialParser, UnconditionalRunner, write_start_rmsd
-from .sample_unconditional_shape import (add_secstruct_arguments, add_shape_arguments, report_fields, restrained_lengths,
-                                         secstruct_constants, secstruct_potential, shape_constants, shape_potential, sum_potentials,
-                                         target_lengths, write_secstruct_report, write_shape_report)
+from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
+from .sample_unconditional_shape import GuidedRunner, add_guidance_arguments, add_secstruct_arguments, add_shape_arguments
 
 
 def load_motif_segments(filepath):
@@ -85,101 +80,47 @@ def write_motif_locations(fit, directory, length, offset):
                     fh.write('# rmsd group {} {:.3f}\n'.format(label, value))
 
 
-class MotifRunner(UnconditionalRunner):
+class MotifRunner(GuidedRunner):
     def create_tasks(self, params):
         total = sum(len(s) for s in load_motif_segments(params['motif_file']))
-        tasks = super().create_tasks(params)
+        tasks = UnconditionalRunner.create_tasks(self, params)
         short = [t['length'] for t in tasks if t['length'] < total]
         if short:
             print('skipping lengths shorter than the {}-residue motif: {}'.format(total, ', '.join(map(str, short))))
-        tasks = [t for t in tasks if t['length'] >= total]
-        return target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
+        return self.guided_lengths([t for t in tasks if t['length'] >= total], params)
 
     def create_constants(self, params):
         c = super().create_constants(params)
-        c.update({k: params[k] for k in ('tausq', 'guidance_alpha', 'ess_threshold', 'last_unguided_steps', 'max_offsets')})
+        c.update({k: params[k] for k in ('tausq', 'max_offsets')})
         c['align'] = params.get('align', 'translation')
         c['write_motif_locations'] = bool(params.get('write_motif_locations', False))
         c['segments'] = load_motif_segments(params['motif_file'])
         c['motif_groups'] = params.get('motif_groups', 'joint')
         c['groups'] = load_motif_groups(params['motif_file']) if c['motif_groups'] == 'file' else None
-        c['num_particles'] = params.get('num_particles')
-        c.update(shape_constants(params))
-        c.update(secstruct_constants(params))
         return c
 
-    def execute(self, constants, tasks, device):
-        from . import capi, pack
-        from .smc import MotifPotential, TwistedSampler
-        model = load_pretrained_model(constants['rootdir'], constants['name'], constants['epoch']).eval().to(device)
-        sampler = TwistedSampler(model)
-        abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
-        for task in tqdm(tasks, desc=device):
-            shape = shape_potential(constants, task['length'], abar, device)
-            secstruct = secstruct_potential(constants, task['length'], abar, device)
-            remaining = constants['num_samples']
-            while remaining > 0:
-                batch = min(constants['batch_size'], remaining)
-                offset = constants['num_samples'] - remaining
-                if constants.get('resume') and all(
-                        os.path.exists(os.path.join(constants['outdir'], 'pdbs', '{}_{}.pdb'.format(task['length'], offset + i)))
-                        for i in range(batch)):
-                    remaining -= batch           # this batch was written by an earlier (interrupted) run
-                    continue
-                # one particle system per batch; its placements drawn from numpy's global generator, as the reference does
-                potential = MotifPotential(constants['segments'], task['length'], abar, tausq=constants['tausq'],
-                                           max_offsets=constants['max_offsets'], device=device, align=constants['align'],
-                                           groups=constants.get('groups'))
-                potential = sum_potentials(potential, shape, secstruct)
-                # (with --num_particles: `batch` systems, each returning its best particle)
-                systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'],
-                                                                             'return_particles': 'best'}
-                sampler.sample({
-                    'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
-                    'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
-                    'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
-                    'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
-                    'num_steps': constants.get('num_steps'), **systems, **self.partial_params(constants)})
-                if constants.get('write_start_rmsd'):
-                    write_start_rmsd(sampler.last_start_rmsd, os.path.join(constants['outdir'], 'start_rmsd'),
-                                     ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
-                if constants['write_motif_locations']:
-                    write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), task['length'], offset)
-                if constants['write_shape_report'] and shape is not None:
-                    write_shape_report(report_fields(sampler.last_shape, capi.SHAPE_REPORT), os.path.join(constants['outdir'], 'shape'),
-                                       task['length'], offset)
-                if constants['write_secstruct'] and secstruct is not None:
-                    write_secstruct_report(sampler.last_secstruct, report_fields(sampler.last_shape, capi.SECSTRUCT_REPORT),
-                                           os.path.join(constants['outdir'], 'secstruct'), task['length'], offset)
-                remaining -= batch
+    def batch_potentials(self, constants, length, abar, device):
+        # one MotifPotential per batch; its placements drawn from numpy's global generator, as the reference does
+        from .smc import MotifPotential
+        return (MotifPotential(constants['segments'], length, abar, tausq=constants['tausq'], max_offsets=constants['max_offsets'],
+                               device=device, align=constants['align'], groups=constants.get('groups')),)
+
+    def after_batch(self, constants, sampler, length, offset):
+        if constants['write_motif_locations']:
+            write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), length, offset)
 
 
 def build_parser():
     p = PartialParser('input_pdb', 'Structure file whose C-alpha backbone every particle starts from')
-    p.add_argument('--name', type=str, help='Model name', required=True)
-    p.add_argument('--epoch', type=int, help='Model epoch', required=True)
-    p.add_argument('--rootdir', type=str, help='Root directory', default='results')
-    p.add_argument('--scale', type=float, help='Sampling noise scale', required=True)
-    p.add_argument('--outdir', type=str, help='Output directory', required=True)
-    p.add_argument('--num_samples', type=int, help='Number of samples per length', default=5)
-    p.add_argument('--batch_size', type=int, help='Batch size', default=4)
-    p.add_argument('--min_length', type=int, help='Minimum sequence length', default=50)
-    p.add_argument('--max_length', type=int, help='Maximum sequence length', default=256)
-    p.add_argument('--length_step', type=int, help='Length step size', default=1)
-    p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
-    p.add_argument('--sequential_order', action='store_true', help='Run in increasing order of length')
+    add_common_arguments(p)
+    tail = ' (not in the reference CLI)'
     p.add_argument('--motif_file', type=str, required=True,
-                   help='Motif problem file (REMARK 999 format, as the scaffold CLI reads); its motif segments guide sampling '
-                        '(not in the reference CLI)')
-    p.add_argument('--tausq', type=float, default=0.012, help='Motif likelihood variance tau^2 (not in the reference CLI)')
-    p.add_argument('--guidance_alpha', type=float, default=0.012, help='Guidance gradient regulariser alpha (not in the reference CLI)')
-    p.add_argument('--ess_threshold', type=float, default=0.5,
-                   help='Resample when the effective sample size falls below this fraction of the batch (not in the reference CLI)')
-    p.add_argument('--last_unguided_steps', type=int, default=50,
-                   help='Steps below this one are not guided (not in the reference CLI)')
+                   help='Motif problem file (REMARK 999 format, as the scaffold CLI reads); its motif segments guide sampling' + tail)
+    p.add_argument('--tausq', type=float, default=0.012, help='Motif likelihood variance tau^2' + tail)
+    add_guidance_arguments(p, tail, 'guidance_alpha', 'ess_threshold', 'last_unguided_steps')
     p.add_argument('--max_offsets', type=int, default=1000,
-                   help='Placements of the motif kept (a random subset when there are more) (not in the reference CLI)')
-    p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist (not in the reference CLI)')
+                   help='Placements of the motif kept (a random subset when there are more)' + tail)
+    add_guidance_arguments(p, tail, 'resume')
     p.add_argument('--align', type=str, choices=('translation', 'rigid'), default='translation',
                    help='Compare placements to the motif as the file orients it (translation) or after optimal superposition (rigid)')
     p.add_argument('--motif_groups', type=str, choices=('joint', 'file'), default='joint',
@@ -188,13 +129,7 @@ def build_parser():
     p.add_argument('--write_motif_locations', action='store_true',
                    help='Write outdir/motif_locations/{length}_{index}.txt: start and end residue of every motif segment in the '
                         'best-fitting placement (0-based, inclusive) and the superposed motif RMSD')
-    p.add_argument('--num_steps', type=int, default=None,
-                   help='Run the reverse process on this many of the n_timestep steps, with the ancestral kernel between them; default: all '
-                        '(an addition to the reference CLI, like --align)')
-    p.add_argument('--num_particles', type=int, default=None,
-                   help='Guide every design as a particle system of its own with this many particles (1..64) and write its best '
-                        'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
-                        'written (an addition to the reference CLI, like --align)')
+    add_guidance_arguments(p, ' (an addition to the reference CLI, like --align)', 'num_steps', 'num_particles')
     add_shape_arguments(p)
     add_secstruct_arguments(p)
     return p

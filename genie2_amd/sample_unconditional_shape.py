@@ -25,7 +25,7 @@ import os
 
 from tqdm import tqdm
 
-from .sample_unconditional import PartialParser, UnconditionalRunner, write_start_rmsd
+from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments, write_start_rmsd
 
 SHAPE_KEYS = ('rog_max', 'rog_weight', 'clash_distance', 'clash_separation', 'clash_weight', 'shape_tausq')
 COUNTS = ('n_clash', 'n_violated')
@@ -86,14 +86,21 @@ def shape_potential(constants, length, abar, device):
                           tausq=constants['shape_tausq'], device=device)
 
 
-def write_shape_report(last_shape, directory, length, offset):
-    """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: a `key value` line per field
-    of TwistedSampler.last_shape, %.3f for Angstrom and energies, %d for counts."""
+def write_report(report, counts, directory, length, offset, headers=None):
+    """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: the line headers[i] when
+    there are headers, then a `key value` line per field of `report`, %d for the fields named in `counts`, %.3f for the others."""
     os.makedirs(directory, exist_ok=True)
-    for i in range(len(next(iter(last_shape.values())))):
+    for i in range(len(next(iter(report.values())))):
         with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
-            for key, column in last_shape.items():
-                fh.write(('{} {:d}\n' if key in COUNTS else '{} {:.3f}\n').format(key, column[i].item()))
+            if headers is not None:
+                fh.write(headers[i] + '\n')
+            for key, column in report.items():
+                fh.write(('{} {:d}\n' if key in counts else '{} {:.3f}\n').format(key, column[i].item()))
+
+
+def write_shape_report(last_shape, directory, length, offset):
+    """write_report of TwistedSampler.last_shape: %.3f for Angstrom and energies, %d for counts."""
+    write_report(last_shape, COUNTS, directory, length, offset)
 
 
 def add_secstruct_arguments(parser):
@@ -172,19 +179,42 @@ def write_secstruct_report(assignment, report, directory, length, offset):
     HEC, then a `key value` line per field of `report` (the secondary-structure fields of last_shape), %.3f for contents and
     energies, %d for counts."""
     from .smc import ss_string
-    os.makedirs(directory, exist_ok=True)
-    for i, row in enumerate(assignment.tolist()):
-        with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
-            fh.write(ss_string(row) + '\n')
-            for key, column in report.items():
-                fh.write(('{} {:d}\n' if key in SECSTRUCT_COUNTS else '{} {:.3f}\n').format(key, column[i].item()))
+    write_report(report, SECSTRUCT_COUNTS, directory, length, offset, [ss_string(row) for row in assignment.tolist()])
 
 
-class ShapeRunner(UnconditionalRunner):
+GUIDANCE_FLAGS = {
+    'guidance_alpha': dict(type=float, default=0.012, help='Guidance gradient regulariser alpha'),
+    'ess_threshold': dict(type=float, default=0.5, help='Resample when the effective sample size falls below this fraction of the batch'),
+    'last_unguided_steps': dict(type=int, default=50, help='Steps below this one are not guided'),
+    'num_steps': dict(type=int, default=None, help='Run the reverse process on this many of the n_timestep steps, with the ancestral '
+                                                   'kernel between them; default: all'),
+    'num_particles': dict(type=int, default=None,
+                          help='Guide every design as a particle system of its own with this many particles (1..64) and write its best '
+                               'particle: --num_samples and --batch_size then count designs; default: one system per batch, every '
+                               'particle written'),
+    'resume': dict(action='store_true', help='Skip batches whose PDB files already exist'),
+}
+
+
+def add_guidance_arguments(parser, tail, *names):
+    """The guidance flags `names` of a guided CLI (all of GUIDANCE_FLAGS when none are named), in that order, each help text ending
+    in `tail`: a CLI that words its tails differently, or lists other flags between these, calls this once per run of flags."""
+    for name in names or GUIDANCE_FLAGS:
+        kw = GUIDANCE_FLAGS[name]
+        parser.add_argument('--' + name, **dict(kw, help=kw['help'] + tail))
+
+
+class GuidedRunner(UnconditionalRunner):
+    """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
+    (a subclass's own, made per batch; none here) and the shape and secondary-structure potentials the constants ask for, in that
+    order; `after_batch` writes a subclass's own reports."""
+
+    def guided_lengths(self, tasks, params):
+        """The tasks whose length the restraints and the blueprint allow."""
+        return target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
+
     def create_tasks(self, params):
-        from .smc import load_restraints
-        restraints = load_restraints(params['restraint_file']) if params.get('restraint_file') else []
-        return target_lengths(restrained_lengths(super().create_tasks(params), restraints), secstruct_constants(params)['ss_target'])
+        return self.guided_lengths(super().create_tasks(params), params)
 
     def create_constants(self, params):
         c = super().create_constants(params)
@@ -192,10 +222,13 @@ class ShapeRunner(UnconditionalRunner):
         c['num_particles'] = params.get('num_particles')
         c.update(shape_constants(params))
         c.update(secstruct_constants(params))
-        if not has_shape_terms(c) and not has_secstruct_terms(c):
-            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, or a secondary-structure '
-                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target)')
         return c
+
+    def batch_potentials(self, constants, length, abar, device):
+        return ()
+
+    def after_batch(self, constants, sampler, length, offset):
+        pass
 
     def execute(self, constants, tasks, device):
         from . import capi, pack
@@ -203,65 +236,44 @@ class ShapeRunner(UnconditionalRunner):
         model = self.load_model(constants, device)
         sampler = TwistedSampler(model)
         abar = pack.schedule_tensors(model.config.diffusion['n_timestep'])['alphas_cumprod'].to(device)
+        # (with --num_particles: `batch` systems, each returning its best particle)
+        systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'], 'return_particles': 'best'}
         for task in tqdm(tasks, desc=device):
-            shape = shape_potential(constants, task['length'], abar, device)
-            secstruct = secstruct_potential(constants, task['length'], abar, device)
-            potential = sum_potentials(shape, secstruct)
-            remaining = constants['num_samples']
-            while remaining > 0:
-                batch = min(constants['batch_size'], remaining)
-                offset = constants['num_samples'] - remaining
-                if constants.get('resume') and all(
-                        os.path.exists(os.path.join(constants['outdir'], 'pdbs', '{}_{}.pdb'.format(task['length'], offset + i)))
-                        for i in range(batch)):
-                    remaining -= batch           # this batch was written by an earlier (interrupted) run
-                    continue
-                # (with --num_particles: `batch` systems, each returning its best particle)
-                systems = {} if constants.get('num_particles') is None else {'num_particles': constants['num_particles'],
-                                                                             'return_particles': 'best'}
+            length, outdir = task['length'], constants['outdir']
+            shape = shape_potential(constants, length, abar, device)
+            secstruct = secstruct_potential(constants, length, abar, device)
+            for batch, offset in self.batches(constants, outdir, length):
                 sampler.sample({
-                    'length': task['length'], 'scale': constants['scale'], 'num_samples': batch,
-                    'outdir': constants['outdir'], 'prefix': str(task['length']), 'offset': offset,
-                    'twisting_function': potential, 'guidance_alpha': constants['guidance_alpha'],
+                    'length': length, 'scale': constants['scale'], 'num_samples': batch,
+                    'outdir': outdir, 'prefix': str(length), 'offset': offset,
+                    'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct),
+                    'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **self.partial_params(constants)})
                 if constants.get('write_start_rmsd'):
-                    write_start_rmsd(sampler.last_start_rmsd, os.path.join(constants['outdir'], 'start_rmsd'),
-                                     ['{}_{}'.format(task['length'], offset + i) for i in range(batch)])
+                    write_start_rmsd(sampler.last_start_rmsd, os.path.join(outdir, 'start_rmsd'),
+                                     ['{}_{}'.format(length, offset + i) for i in range(batch)])
+                self.after_batch(constants, sampler, length, offset)
                 if constants['write_shape_report'] and shape is not None:
-                    write_shape_report(report_fields(sampler.last_shape, capi.SHAPE_REPORT), os.path.join(constants['outdir'], 'shape'),
-                                       task['length'], offset)
+                    write_shape_report(report_fields(sampler.last_shape, capi.SHAPE_REPORT), os.path.join(outdir, 'shape'), length, offset)
                 if constants['write_secstruct'] and secstruct is not None:
                     write_secstruct_report(sampler.last_secstruct, report_fields(sampler.last_shape, capi.SECSTRUCT_REPORT),
-                                           os.path.join(constants['outdir'], 'secstruct'), task['length'], offset)
-                remaining -= batch
+                                           os.path.join(outdir, 'secstruct'), length, offset)
+
+
+class ShapeRunner(GuidedRunner):
+    def create_constants(self, params):
+        c = super().create_constants(params)
+        if not has_shape_terms(c) and not has_secstruct_terms(c):
+            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, or a secondary-structure '
+                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target)')
+        return c
 
 
 def build_parser():
     p = PartialParser('input_pdb', 'Structure file whose C-alpha backbone every particle starts from')
-    p.add_argument('--name', type=str, help='Model name', required=True)
-    p.add_argument('--epoch', type=int, help='Model epoch', required=True)
-    p.add_argument('--rootdir', type=str, help='Root directory', default='results')
-    p.add_argument('--scale', type=float, help='Sampling noise scale', required=True)
-    p.add_argument('--outdir', type=str, help='Output directory', required=True)
-    p.add_argument('--num_samples', type=int, help='Number of samples per length', default=5)
-    p.add_argument('--batch_size', type=int, help='Batch size', default=4)
-    p.add_argument('--min_length', type=int, help='Minimum sequence length', default=50)
-    p.add_argument('--max_length', type=int, help='Maximum sequence length', default=256)
-    p.add_argument('--length_step', type=int, help='Length step size', default=1)
-    p.add_argument('--num_devices', type=int, help='Number of GPU devices', default=1)
-    p.add_argument('--sequential_order', action='store_true', help='Run in increasing order of length')
-    p.add_argument('--resume', action='store_true', help='Skip batches whose PDB files already exist')
-    p.add_argument('--guidance_alpha', type=float, default=0.012, help='Guidance gradient regulariser alpha')
-    p.add_argument('--ess_threshold', type=float, default=0.5,
-                   help='Resample when the effective sample size falls below this fraction of the batch')
-    p.add_argument('--last_unguided_steps', type=int, default=50, help='Steps below this one are not guided')
-    p.add_argument('--num_steps', type=int, default=None,
-                   help='Run the reverse process on this many of the n_timestep steps, with the ancestral kernel between them; default: all')
-    p.add_argument('--num_particles', type=int, default=None,
-                   help='Guide every design as a particle system of its own with this many particles (1..64) and write its best '
-                        'particle: --num_samples and --batch_size then count designs; default: one system per batch, every particle '
-                        'written')
+    add_common_arguments(p)
+    add_guidance_arguments(p, '', 'resume', 'guidance_alpha', 'ess_threshold', 'last_unguided_steps', 'num_steps', 'num_particles')
     add_shape_arguments(p)
     add_secstruct_arguments(p)
     return p

@@ -11,10 +11,13 @@ is not differentiable) the third, and SumPotential adds potentials.
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
 potential reproduces the ancestral sampler, (c) that the guided gradient equals torch autograd through the oracle."""
+import ctypes as C
 import numbers
+import types
 
 import torch
 
+from . import capi
 from . import features as F
 from . import pack
 from .sampler import UnconditionalSampler, start_rmsd
@@ -138,6 +141,9 @@ class TwistedSampler(UnconditionalSampler):
     weights are ratios of the Gaussian transition densities of the ancestral kernel.
     A model with triangular attention is refused at construction: the guidance needs the denoiser's VJP, which is not built for it.
 
+    One loop serves every variant: _setup builds the run's state, guided_step (below the class) is the guided half of an iteration,
+    _host_update or one SmcReweight call its SMC bookkeeping, _finish the reports.
+
     Optional 'num_particles' = K in 1..64 (not in the reference; the fork's latest sampler has the layout) makes 'num_samples' = S
     independent particle systems of K particles each in one device batch of S K, system-major (particle b belongs to system b // K):
     weights, ESS, resampling and the gradient-norm cap are per system, and the SMC bookkeeping of a step is one genie_smc_reweight
@@ -170,20 +176,18 @@ class TwistedSampler(UnconditionalSampler):
         plan = super().few_step_plan(params)
         return None if plan is None else (plan[0], pack.twisted_coefficients(self.model.config.diffusion['n_timestep'], plan[0]))
 
-    def _sample(self, params):
-        if params.get('num_particles') is not None or params.get('return_particles') is not None:
-            return self._sample_systems(params)
-        plan = self.few_step_plan(params)
+    def _setup(self, params, steps, coef, B, S=None):
+        """The state of a run over `steps` (`coef`: their rows of pack.twisted_coefficients on the host, or None) with a device
+        batch of B, as S systems (None: one system, the whole batch): what guided_step reads, and the start of the loop --
+        trans, rots, log_proposal, log_w_acc."""
         m = self.model
-        T = m.config.diffusion['n_timestep']
-        steps = list(range(self.partial_start(params) or T, 0, -1)) if plan is None else plan[0]
-        np_feats = F.batchify_np_features([self.create_np_features(params) for _ in range(params['num_samples'])])
+        np_feats = F.batchify_np_features([self.create_np_features(params) for _ in range(B)])
         partial = self.partial_inputs(params, np_feats, len(steps))
         feats = F.convert_np_features_to_tensor(np_feats, self.device)
-        B, N = feats['residue_mask'].shape
-        tw_coef = None if plan is None else plan[1].to(device=self.device, dtype=torch.float32)
-        sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(T).items()}
-        abar, betas = sched['alphas_cumprod'], sched['betas']
+        N = feats['residue_mask'].shape[1]
+        tw_coef = None if coef is None else coef.to(device=self.device, dtype=torch.float32)
+        sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(m.config.diffusion['n_timestep']).items()}
+        abar = sched['alphas_cumprod']
         noise = params.get('noise')
         draw = (lambda k: noise[k].to(self.device)) if noise is not None else (lambda k: torch.randn(B, N, 3, device=self.device))
         twist = params.get('twisting_function')
@@ -194,170 +198,44 @@ class TwistedSampler(UnconditionalSampler):
             tgt = tgt - tgt.mean(dim=0, keepdim=True)
             tausq = float(params.get('tausq', 0.012))
             twist = lambda x0, step: motif_twisting_function(x0, pm, tgt, abar[step], tausq)      # noqa: E731
-        alpha = float(params.get('guidance_alpha', 0.012))
         eng = m.model.bind(feats)
         w = pack.flatten_state_dict(m.model.state_dict(), m.model.dims).to(self.device)
         mask = feats['residue_mask'].unsqueeze(-1).float()
         trans = draw(0)
         log_proposal = log_normal_density(trans, torch.tensor(0., device=self.device), torch.tensor(1., device=self.device)).sum(dim=(1, 2))
-        log_w_acc = torch.zeros(B, device=self.device)
         if partial is None:
             rots = eng.frenet(trans)
         else:           # trans was the forward draw noise[0]: log_proposal is its density (the class docstring), the state q_sample's
             trans, rots = self.start_state(eng, partial[1], trans.float() * mask, partial[0])
-        self.ess_trace, self.resampled_at = [], []
-        us = list(params.get('resample_u', []))
-        for it, step in enumerate(steps):
-            ts = torch.full((B,), step, dtype=torch.int32, device=self.device)
-            c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
-            z = eng.denoise(trans, rots, ts)['z']
-            x0 = ((trans - c1 * z) / c0).detach().requires_grad_(True)          # E[x_0 | x_t] (:474)
-            log_prob = twist(x0, step)
-            g = torch.autograd.grad(log_prob.mean(), x0)[0] * B                   # (:480-482, "rescale mean back")
-            # chain rule through x0(trans) = (trans - c1 z(trans)) / c0 with the frames fixed: the part through z is the HIP VJP
-            _, dz_part = eng.denoise_vjp(w, trans, rots, ts, (-c1 / c0) * g)
-            grad = g / c0 + dz_part
-            norm = grad.double().norm().float()                                   # (f64: the f32 sum of squares overflows before the cap below acts)
-            grad = grad * alpha * norm / (alpha + norm)                           # (:483-488)
-            x0u = x0.detach()
-            x0t = x0u + grad if step >= int(params.get('last_unguided_steps', 50)) else x0u
-            if tw_coef is None:
-                coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
-                coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
-                sigma = sched['sqrt_betas'][step]
-            else:           # the same posterior between step and the next visited one (float64 on the host, pack.twisted_coefficients)
-                coef1, coef2, sigma = tw_coef[it]
-            mean_t, mean_u = coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans
-            if it == len(steps) - 1:
-                trans = mean_t
-                break
-            new = (mean_t + params['scale'] * sigma * draw(it + 1)) * mask
-            log_rev = log_normal_density(new, mean_u, sigma ** 2).sum(dim=(1, 2))
-            log_tw = log_normal_density(new, mean_t, sigma ** 2).sum(dim=(1, 2))
-            log_w = (log_rev + log_prob.detach() - log_tw) - log_proposal
-            log_proposal = log_prob.detach()
-            log_w_acc = log_w + log_w_acc
-            ess = compute_ess_from_log_w(log_w_acc)
-            self.ess_trace.append(float(ess))
-            if ess < float(params.get('ess_threshold', 0.5)) * B:
-                new, log_w_acc, idx = systematic_resampling(new, torch.softmax(log_w_acc, dim=0), us.pop(0) if us else None)
-                log_proposal = log_proposal[idx.to(self.device)]
-                self.resampled_at.append(step)
-            else:
-                log_w_acc = normalize_log_weights(log_w_acc, dim=0) + torch.log(torch.tensor(float(B), device=self.device))
-            trans = new
-            rots = eng.frenet(trans)
-        # where the motif ended up (MotifPotential.locate: the best placement of every sample and its superposed RMSD)
-        self.last_fit = None
-        if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
-            self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans.detach()).items()}
-        self.last_shape = {k: v.cpu() for k, v in twist.describe(trans.detach()).items()} if hasattr(twist, 'describe') else None
-        self.last_secstruct = twist.assign(trans.detach()).cpu() if hasattr(twist, 'assign') else None
-        feats['atom_positions'] = trans.detach().cpu()
-        self.last_start_rmsd = None if partial is None else start_rmsd(feats['atom_positions'], partial[1], feats['residue_mask'])
-        return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
+        return types.SimpleNamespace(
+            steps=steps, tw_coef=tw_coef, sched=sched, feats=feats, partial=partial, draw=draw, twist=twist, eng=eng, w=w, mask=mask,
+            S=S, alpha=float(params.get('guidance_alpha', 0.012)), unguided=int(params.get('last_unguided_steps', 50)),
+            ess_fraction=float(params.get('ess_threshold', 0.5)), trans=trans, rots=rots, log_proposal=log_proposal,
+            log_w_acc=torch.zeros(B, device=self.device))
 
-    def _sample_systems(self, params):
-        """_sample for params['num_particles'] = K: S = num_samples independent systems of K particles (the class docstring).  The
-        loop body is _sample's, with the norm cap per system and lines "new = ..." to "trans = new" as one genie_smc_reweight call."""
-        K, S, keep = params.get('num_particles'), params['num_samples'], params.get('return_particles', 'all')
-        if K is None:
-            raise ValueError("return_particles=%r needs num_particles" % (keep,))
-        if isinstance(K, bool) or not isinstance(K, numbers.Integral) or not 1 <= K <= SMC_MAX_PARTICLES:
-            raise ValueError('num_particles must be an integer in 1..%d, got %r' % (SMC_MAX_PARTICLES, K))
-        if keep not in ('all', 'best'):
-            raise ValueError("return_particles must be 'all' or 'best', got %r" % (keep,))
-        K = int(K)
-        plan = self.few_step_plan(params)
-        m = self.model
-        T = m.config.diffusion['n_timestep']
-        steps = list(range(self.partial_start(params) or T, 0, -1)) if plan is None else plan[0]
-        noise = params.get('noise')
-        if noise is not None and (noise.dim() != 4 or noise.shape[0] != len(steps) or noise.shape[1] != S * K):
-            raise ValueError('noise must be [%d, %d, N, 3] with num_samples=%d and num_particles=%d, got %s'
-                             % (len(steps), S * K, S, K, tuple(noise.shape)))
-        us = list(params.get('resample_u', []))
-        us = [[float(e)] * S if _is_scalar(e) else [float(v) for v in e] for e in us]
-        if any(len(e) != S for e in us):
-            raise ValueError('an entry of resample_u is a scalar or %d values, one per system' % S)
-        np_feats = F.batchify_np_features([self.create_np_features(params) for _ in range(S * K)])
-        partial = self.partial_inputs(params, np_feats, len(steps))
-        feats = F.convert_np_features_to_tensor(np_feats, self.device)
-        B, N = feats['residue_mask'].shape
-        tw_coef = None if plan is None else plan[1].to(device=self.device, dtype=torch.float32)
-        sched = {k: v.to(self.device) for k, v in pack.schedule_tensors(T).items()}
-        abar, betas = sched['alphas_cumprod'], sched['betas']
-        draw = (lambda k: noise[k].to(self.device)) if noise is not None else (lambda k: torch.randn(B, N, 3, device=self.device))
-        twist = params.get('twisting_function')
-        if twist is None:
-            segs = [torch.as_tensor(x, dtype=torch.float32) for x in params['motif_target']]
-            pm = placement_masks(generate_motif_index_mask(segs, N)).to(self.device)
-            tgt = torch.cat(segs).to(self.device)
-            tgt = tgt - tgt.mean(dim=0, keepdim=True)
-            tausq = float(params.get('tausq', 0.012))
-            twist = lambda x0, step: motif_twisting_function(x0, pm, tgt, abar[step], tausq)      # noqa: E731
-        alpha = float(params.get('guidance_alpha', 0.012))
-        ess_fraction = float(params.get('ess_threshold', 0.5))
-        eng = m.model.bind(feats)
-        w = pack.flatten_state_dict(m.model.state_dict(), m.model.dims).to(self.device)
-        mask = feats['residue_mask'].unsqueeze(-1).float()
-        trans = draw(0)
-        log_proposal = log_normal_density(trans, torch.tensor(0., device=self.device), torch.tensor(1., device=self.device)).sum(dim=(1, 2))
-        log_w_acc = torch.zeros(B, device=self.device)
-        if partial is None:
-            rots = eng.frenet(trans)
-        else:           # trans was the forward draw noise[0]: log_proposal is its density (the class docstring), the state q_sample's
-            trans, rots = self.start_state(eng, partial[1], trans.float() * mask, partial[0])
-        reweight = SmcReweight(S, K, N, self.device)
-        ess_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.float32, device=self.device)
-        resampled_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.int32, device=self.device)
-        for it, step in enumerate(steps):
-            ts = torch.full((B,), step, dtype=torch.int32, device=self.device)
-            c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
-            z = eng.denoise(trans, rots, ts)['z']
-            x0 = ((trans - c1 * z) / c0).detach().requires_grad_(True)
-            log_prob = twist(x0, step)
-            g = torch.autograd.grad(log_prob.mean(), x0)[0] * B
-            _, dz_part = eng.denoise_vjp(w, trans, rots, ts, (-c1 / c0) * g)
-            grad = g / c0 + dz_part
-            # the cap of (:483-488) over a system's own K particles: a system's step must not depend on its batch neighbours
-            norm = grad.double().view(S, -1).norm(dim=1).float().view(S, 1, 1, 1)
-            grad = (grad.view(S, K, N, 3) * alpha * norm / (alpha + norm)).view(B, N, 3)
-            x0u = x0.detach()
-            x0t = x0u + grad if step >= int(params.get('last_unguided_steps', 50)) else x0u
-            if tw_coef is None:
-                coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
-                coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
-                sigma = sched['sqrt_betas'][step]
-            else:
-                coef1, coef2, sigma = tw_coef[it]
-            mean_t, mean_u = coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans
-            if it == len(steps) - 1:
-                trans = mean_t
-                break
-            new = (mean_t + params['scale'] * sigma * draw(it + 1)) * mask
-            if it < len(us):
-                u = torch.tensor(us[it], dtype=torch.float32).to(self.device)
-            else:
-                u = torch.rand(S, device=self.device) / K
-            trans, _ = reweight(new, mean_t, mean_u, sigma, log_prob.detach(), u, ess_fraction, log_proposal, log_w_acc,
-                                ess_out=ess_dev[it], resampled_out=resampled_dev[it])
-            rots = eng.frenet(trans)
-        # the one host read of the run
-        self.ess_trace = ess_dev.cpu()
-        flags = resampled_dev.cpu()
-        self.resampled_at = [[steps[it] for it in range(flags.shape[0]) if int(flags[it, s])] for s in range(S)]
-        self.last_log_weights = log_w_acc.detach().cpu().view(S, K)
-        top = self.last_log_weights == self.last_log_weights.max(dim=1, keepdim=True).values
-        first = torch.where(top, torch.arange(K).expand(S, K), torch.full((S, K), K)).min(dim=1).values
-        self.last_choice = torch.where(first < K, first, torch.zeros_like(first))       # (no entry equals a NaN max: particle 0)
-        trans = trans.detach()
-        start = None if partial is None else partial[1]
-        if keep == 'best':
-            pick = (torch.arange(S) * K + self.last_choice).to(self.device)
-            trans = trans[pick]
-            start = None if start is None else start[pick.cpu()]
-            feats = {k: (v[pick] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for k, v in feats.items()}
+    def _host_update(self, st, step, new, mean_t, mean_u, sigma, log_prob, us):
+        """The SMC bookkeeping of one system of B = the whole batch, in torch with one host read (the ESS): the weight update, then
+        systematic resampling (its uniform from `us`, else drawn on the host) or the renormalisation.  Returns the next particles."""
+        B = new.shape[0]
+        log_rev = log_normal_density(new, mean_u, sigma ** 2).sum(dim=(1, 2))
+        log_tw = log_normal_density(new, mean_t, sigma ** 2).sum(dim=(1, 2))
+        log_w = (log_rev + log_prob - log_tw) - st.log_proposal
+        st.log_proposal = log_prob
+        st.log_w_acc = log_w + st.log_w_acc
+        ess = compute_ess_from_log_w(st.log_w_acc)
+        self.ess_trace.append(float(ess))
+        if ess < st.ess_fraction * B:
+            new, st.log_w_acc, idx = systematic_resampling(new, torch.softmax(st.log_w_acc, dim=0), us.pop(0) if us else None)
+            st.log_proposal = st.log_proposal[idx.to(self.device)]
+            self.resampled_at.append(step)
+        else:
+            st.log_w_acc = normalize_log_weights(st.log_w_acc, dim=0) + torch.log(torch.tensor(float(B), device=self.device))
+        return new
+
+    def _finish(self, st, trans, feats, start):
+        """The reports on the returned coordinates `trans` (MotifPotential.locate: the best placement of every sample and its
+        superposed RMSD; describe; assign; the RMSD to `start`) and the features to write."""
+        twist = st.twist
         self.last_fit = None
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans).items()}
@@ -367,6 +245,105 @@ class TwistedSampler(UnconditionalSampler):
         self.last_start_rmsd = None if start is None else start_rmsd(feats['atom_positions'], start, feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 
+    def _sample(self, params):
+        K, S = params.get('num_particles'), None
+        if K is not None or params.get('return_particles') is not None:       # S = num_samples systems of K particles (the class docstring)
+            keep = params.get('return_particles', 'all')
+            if K is None:
+                raise ValueError("return_particles=%r needs num_particles" % (keep,))
+            if isinstance(K, bool) or not isinstance(K, numbers.Integral) or not 1 <= K <= SMC_MAX_PARTICLES:
+                raise ValueError('num_particles must be an integer in 1..%d, got %r' % (SMC_MAX_PARTICLES, K))
+            if keep not in ('all', 'best'):
+                raise ValueError("return_particles must be 'all' or 'best', got %r" % (keep,))
+            K, S = int(K), params['num_samples']
+        plan = self.few_step_plan(params)
+        steps = list(range(self.partial_start(params) or self.model.config.diffusion['n_timestep'], 0, -1)) if plan is None else plan[0]
+        us = list(params.get('resample_u', []))
+        if S is not None:
+            noise = params.get('noise')
+            if noise is not None and (noise.dim() != 4 or noise.shape[0] != len(steps) or noise.shape[1] != S * K):
+                raise ValueError('noise must be [%d, %d, N, 3] with num_samples=%d and num_particles=%d, got %s'
+                                 % (len(steps), S * K, S, K, tuple(noise.shape)))
+            us = [[float(e)] * S if _is_scalar(e) else [float(v) for v in e] for e in us]
+            if any(len(e) != S for e in us):
+                raise ValueError('an entry of resample_u is a scalar or %d values, one per system' % S)
+        st = self._setup(params, steps, None if plan is None else plan[1], params['num_samples'] if S is None else S * K, S)
+        feats, trans, rots = st.feats, st.trans, st.rots
+        B, N = feats['residue_mask'].shape
+        if S is None:
+            self.ess_trace, self.resampled_at = [], []
+        else:
+            reweight = SmcReweight(S, K, N, self.device)
+            ess_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.float32, device=self.device)
+            resampled_dev = torch.zeros(max(len(steps) - 1, 0), S, dtype=torch.int32, device=self.device)
+        for it, step in enumerate(steps):
+            mean_t, mean_u, sigma, log_prob = guided_step(st, it, step, trans, rots)
+            if it == len(steps) - 1:
+                trans = mean_t
+                break
+            new = (mean_t + params['scale'] * sigma * st.draw(it + 1)) * st.mask
+            if S is None:
+                trans = self._host_update(st, step, new, mean_t, mean_u, sigma, log_prob, us)
+            else:       # the same bookkeeping per system as one genie_smc_reweight call, no host read
+                if it < len(us):
+                    u = torch.tensor(us[it], dtype=torch.float32).to(self.device)
+                else:
+                    u = torch.rand(S, device=self.device) / K
+                trans, _ = reweight(new, mean_t, mean_u, sigma, log_prob, u, st.ess_fraction, st.log_proposal, st.log_w_acc,
+                                    ess_out=ess_dev[it], resampled_out=resampled_dev[it])
+            rots = st.eng.frenet(trans)
+        trans = trans.detach()
+        start = None if st.partial is None else st.partial[1]
+        if S is not None:
+            # the one host read of the run
+            self.ess_trace = ess_dev.cpu()
+            flags = resampled_dev.cpu()
+            self.resampled_at = [[steps[it] for it in range(flags.shape[0]) if int(flags[it, s])] for s in range(S)]
+            self.last_log_weights = st.log_w_acc.detach().cpu().view(S, K)
+            top = self.last_log_weights == self.last_log_weights.max(dim=1, keepdim=True).values
+            first = torch.where(top, torch.arange(K).expand(S, K), torch.full((S, K), K)).min(dim=1).values
+            self.last_choice = torch.where(first < K, first, torch.zeros_like(first))       # (no entry equals a NaN max: particle 0)
+            if keep == 'best':
+                pick = (torch.arange(S) * K + self.last_choice).to(self.device)
+                trans = trans[pick]
+                start = None if start is None else start[pick.cpu()]
+                feats = {k: (v[pick] if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B else v) for k, v in feats.items()}
+        return self._finish(st, trans, feats, start)
+
+
+def guided_step(state, it, step, trans, rots):
+    """The guided half of iteration `it` of TwistedSampler's loop, at timestep `step`: the denoiser's E[x_0 | x_t], the potential and
+    its gradient through the denoiser, capped in norm, and the posterior between `step` and the next visited one.  Returns
+    (mean_t, mean_u, sigma, log_prob): the twisted and the unguided mean, the posterior's standard deviation, log p(y | x_t) [B]
+    detached.  `state` holds eng, w, sched, tw_coef, twist, alpha, unguided and S (TwistedSampler._setup); with S systems the cap is
+    over a system's own particles, with S = None over the whole batch."""
+    st, B = state, trans.shape[0]
+    abar, betas = st.sched['alphas_cumprod'], st.sched['betas']
+    ts = torch.full((B,), step, dtype=torch.int32, device=trans.device)
+    c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
+    z = st.eng.denoise(trans, rots, ts)['z']
+    x0 = ((trans - c1 * z) / c0).detach().requires_grad_(True)          # E[x_0 | x_t] (:474)
+    log_prob = st.twist(x0, step)
+    g = torch.autograd.grad(log_prob.mean(), x0)[0] * B                   # (:480-482, "rescale mean back")
+    # chain rule through x0(trans) = (trans - c1 z(trans)) / c0 with the frames fixed: the part through z is the HIP VJP
+    _, dz_part = st.eng.denoise_vjp(st.w, trans, rots, ts, (-c1 / c0) * g)
+    grad = g / c0 + dz_part
+    if st.S is None:
+        norm = grad.double().norm().float()                               # (f64: the f32 sum of squares overflows before the cap below acts)
+    else:       # over a system's own particles: a system's step must not depend on its batch neighbours
+        norm = grad.double().view(st.S, -1).norm(dim=1).float().view(st.S, 1, 1, 1)
+        grad = grad.view(st.S, B // st.S, *grad.shape[1:])
+    grad = (grad * st.alpha * norm / (st.alpha + norm)).view(x0.shape)   # (:483-488)
+    x0u = x0.detach()
+    x0t = x0u + grad if step >= st.unguided else x0u
+    if st.tw_coef is None:
+        coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
+        coef2 = st.sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
+        sigma = st.sched['sqrt_betas'][step]
+    else:           # the same posterior between step and the next visited one (float64 on the host, pack.twisted_coefficients)
+        coef1, coef2, sigma = st.tw_coef[it]
+    return coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans, sigma, log_prob.detach()
+
 
 SMC_MAX_PARTICLES = 64          # K of genie_smc_reweight: one wave holds a system
 
@@ -375,7 +352,36 @@ def _is_scalar(x):
     return isinstance(x, numbers.Real) or (torch.is_tensor(x) and x.dim() == 0)
 
 
-class SmcReweight:
+def _ptr(t):
+    """A tensor's data pointer as a C entry takes it; NULL for None."""
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+class _HipEntry:
+    """What a class that launches libgenie_hip entries holds: the library, its GPU device and the checked call."""
+
+    def _bind(self, device, name):
+        """Load the library and normalise `device`, which must be a GPU (`name` is who says so): its index is filled in."""
+        self.lib = capi.load_library()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise capi.GenieError('%s runs on the GPU (libgenie_hip); there is no CPU path' % name)
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _call(self, name, *args):
+        """Run the entry `name` with the device current; a non-zero return is a GenieError with the library's message."""
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(*args)
+        if rc != 0:
+            msg = self.lib.genie_last_error(None)
+            raise capi.GenieError('%s failed (%d): %s' % (name, rc, msg.decode() if msg else '?'))
+
+
+class SmcReweight(_HipEntry):
     """genie_smc_reweight (include/genie_hip.h) for S systems of K particles of N residues on `device`: one call does, per system,
     what smc.py's loop does after the draw -- the weight update, the ESS, systematic resampling below `ess_fraction` K or the
     renormalisation above it -- on torch's current stream, without a host read.  `log_proposal` and `log_w_acc` [S K] are updated in
@@ -383,14 +389,8 @@ class SmcReweight:
     resampling flag of every system in `ess_out` / `resampled_out` [S] (its own `ess`, `resampled` when none are given)."""
 
     def __init__(self, S, K, N, device='cuda'):
-        from . import capi
-        self.lib = capi.load_library()
         self.S, self.K, self.N = int(S), int(K), int(N)
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise capi.GenieError('genie_smc_reweight runs on the GPU (libgenie_hip); there is no CPU path')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        self._bind(device, 'genie_smc_reweight')
         need = self.lib.genie_smc_reweight_work_bytes(self.S, self.K, self.N)
         if need == 0:
             raise ValueError('S = %d, K = %d, N = %d: needs S, N >= 1 and K in 1..%d' % (self.S, self.K, self.N, SMC_MAX_PARTICLES))
@@ -400,7 +400,6 @@ class SmcReweight:
 
     def __call__(self, x_new, mean_tw, mean_un, sigma, log_prob, u, ess_fraction, log_proposal, log_w_acc, ess_out=None,
                  resampled_out=None, x_out=None, work_bytes=None):
-        import ctypes as C
         B, f32 = self.S * self.K, torch.float32
         ess_out = self.ess if ess_out is None else ess_out
         resampled_out = self.resampled if resampled_out is None else resampled_out
@@ -415,16 +414,9 @@ class SmcReweight:
                                  % (dtype, shape, self.device, t.dtype, tuple(t.shape), t.device))
         x_out = torch.empty_like(ins[0]) if x_out is None else x_out
         index = torch.empty(B, dtype=torch.int32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
-        with torch.cuda.device(self.device):
-            rc = self.lib.genie_smc_reweight(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), self.S, self.K, self.N,
-                                             p(ins[0]), p(ins[1]), p(ins[2]), p(sigma), p(log_prob), p(u), float(ess_fraction),
-                                             p(log_proposal), p(log_w_acc), p(x_out), p(index), p(ess_out), p(resampled_out),
-                                             p(self.work), self.work.numel() * 8 if work_bytes is None else work_bytes)
-        if rc != 0:
-            from . import capi
-            msg = self.lib.genie_last_error(None)
-            raise capi.GenieError('genie_smc_reweight failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        self._call('genie_smc_reweight', self._stream(), self.S, self.K, self.N, *(_ptr(t) for t in ins), _ptr(sigma), _ptr(log_prob),
+                   _ptr(u), float(ess_fraction), _ptr(log_proposal), _ptr(log_w_acc), _ptr(x_out), _ptr(index), _ptr(ess_out),
+                   _ptr(resampled_out), _ptr(self.work), self.work.numel() * 8 if work_bytes is None else work_bytes)
         return x_out, index
 
 
@@ -470,7 +462,7 @@ def _check_starts(starts, seg_len, n_res):
         raise ValueError('a placement leaves 0..%d or puts its segments out of order' % (n_res - 1))
 
 
-class _MotifPotentialFn(torch.autograd.Function):
+class _PotentialFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, pot, var):
         logp, grad = pot._launch(pot._checked(x0), var)
@@ -483,7 +475,45 @@ class _MotifPotentialFn(torch.autograd.Function):
         return grad_output[:, None, None] * grad, None, None
 
 
-class MotifPotential:
+class _HipPotential(_HipEntry):
+    """What the built-in potentials share: `pot(x0 [B,N,3], step) -> log p [B]` through the subclass's `_launch(x, var)`, which
+    returns (logp, grad) of one C entry; the forward keeps that gradient and the backward scales it.  A subclass validates its
+    arguments on the host and then calls this constructor, which is the first to look at the device.  (No `locate`, `describe`,
+    `assign` or `has_fit` here: TwistedSampler and SumPotential take a potential to report what it has a method for.)"""
+
+    def __init__(self, n_res, alphas_cumprod, tausq, device):
+        self._bind(device, type(self).__name__)
+        self.n_res, self.tausq = int(n_res), float(tausq)
+        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
+        self._work = torch.zeros(0, dtype=torch.uint8, device=self.device)
+        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+
+    def variance(self, step):
+        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
+
+    def __call__(self, x0, step):
+        return _PotentialFn.apply(x0, self, self.variance(step))
+
+    def _checked(self, x0):
+        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
+            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
+        if x0.device != self.device:
+            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
+        return x0.detach().to(torch.float32).contiguous()
+
+    def _workspace(self, need):
+        """The entry's `work` arguments (pointer, bytes): a device buffer of at least `need` bytes, grown on demand; NULL for 0."""
+        if need > self._work.numel():
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return _ptr(self._work if need else None), self._work.numel()
+
+
+def _decode_report(report, names, count_names):
+    """A [B, len(names)] report of a C entry as {name: [B]}: int64 for the `count_names`, a copy of the column otherwise."""
+    return {k: report[:, i].round().long() if k in count_names else report[:, i].clone() for i, k in enumerate(names)}
+
+
+class MotifPotential(_HipPotential):
     """The motif twisting function of unconditional_smc.py:303-345 (motif_twisting_function above) as one HIP pass over every
     placement: `pot(x0 [B,N,3], step) -> log p(y | x0) [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler.
 
@@ -506,11 +536,9 @@ class MotifPotential:
 
     def __init__(self, segments, n_res, alphas_cumprod, tausq=0.012, max_offsets=1000, rng=None, device='cuda', align='translation',
                  groups=None):
-        from . import capi
         if align not in ('translation', 'rigid'):
             raise ValueError("align must be 'translation' or 'rigid', got %r" % (align,))
         self.align = align
-        self.lib = capi.load_library()
         segs = [torch.as_tensor(x, dtype=torch.float32).reshape(-1, 3) for x in segments]
         self.seg_len = [len(x) for x in segs]
         if not segs or min(self.seg_len) < 1:
@@ -528,12 +556,7 @@ class MotifPotential:
         elif align == 'rigid':
             for g, label in enumerate(self.groups):
                 _check_superposable(torch.cat([x for x, i in zip(segs, self.seg_group) if i == g]), ' in group %r' % (label,))
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise capi.GenieError('MotifPotential runs on the GPU (libgenie_hip); there is no CPU path')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self.n_res, self.tausq = int(n_res), float(tausq)
+        super().__init__(n_res, alphas_cumprod, tausq, device)
         self.locs = get_all_motif_locations(self.n_res, self.seg_len, max_offsets, rng)
         if not self.locs:
             raise ValueError('a motif of %d residues does not fit in %d' % (sum(self.seg_len), self.n_res))
@@ -544,20 +567,11 @@ class MotifPotential:
         self.seg_len_t = torch.tensor(self.seg_len, dtype=torch.int32, device=self.device)
         tgt = torch.cat(segs).to(self.device)
         self.target = (tgt - tgt.mean(dim=0, keepdim=True)).contiguous()      # (as TwistedSampler, smc.py:133-140)
-        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
-        self._work = torch.zeros(0, dtype=torch.uint8, device=self.device)
-        self.has_fit = self.M >= 3                                      # locate() superposes: three residues at least
+        self.has_fit = self.M >= 3                                    # locate() superposes: three residues at least
         if self.groups is not None:
             self.G = len(self.groups)
             self.seg_group_t = torch.tensor(self.seg_group, dtype=torch.int32, device=self.device)
             self.has_fit = min(sum(n for n, g in zip(self.seg_len, self.seg_group) if g == k) for k in range(self.G)) >= 3
-        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-
-    def variance(self, step):
-        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
-
-    def __call__(self, x0, step):
-        return _MotifPotentialFn.apply(x0, self, self.variance(step))
 
     def locate(self, x):
         """Where the motif is in x [B,N,3]: {'best' [B]: the placement that fits best after optimal superposition (the lowest
@@ -576,53 +590,37 @@ class MotifPotential:
             fit.update(group_rmsd=group_rmsd[0], groups=list(self.groups))
         return fit
 
-    def _checked(self, x0):
-        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
-            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
-        if x0.device != self.device:
-            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
-        return x0.detach().to(torch.float32).contiguous()
-
     def _entry(self, x, var, fit):
         """The C entry that (`groups`, `align`, `fit`) select, for x (f32, contiguous): (its name, the `work` bytes it needs, its
         arguments up to `work`, its outputs).  The outputs are freshly allocated, in the entry's order logp, grad, best, rmsd
         [, group_rmsd]: the fit when `fit` (always superposed), else the potential; the other half is None and passed as NULL."""
-        import ctypes as C
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
         B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
         rigid = fit or self.align == 'rigid'
-        head = (C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x), self.P, self.S, self.M)
-        tail = (p(self.starts), p(self.target), p(var))
+        head = (self._stream(), B, self.n_res, _ptr(x), self.P, self.S, self.M)
+        tail = (_ptr(self.starts), _ptr(self.target), _ptr(var))
         if self.groups is not None:
             name, n_out = 'genie_motif_potential_grouped', 5
             need = self.lib.genie_motif_potential_grouped_work_bytes(B, self.P, self.G, int(rigid))
-            args = head + (self.G, p(self.seg_len_t), p(self.seg_group_t)) + tail + (int(rigid),)
+            args = head + (self.G, _ptr(self.seg_len_t), _ptr(self.seg_group_t)) + tail + (int(rigid),)
         elif rigid:
             name, n_out = 'genie_motif_potential_rigid', 4
             need = self.lib.genie_motif_potential_rigid_work_bytes(B, self.P)
-            args = head + (p(self.seg_len_t),) + tail
+            args = head + (_ptr(self.seg_len_t),) + tail
         else:
             name, n_out = 'genie_motif_potential', 2
             need = self.lib.genie_motif_potential_work_bytes(B, self.P)
-            args = head + (p(self.seg_len_t),) + tail
+            args = head + (_ptr(self.seg_len_t),) + tail
         if fit:
             outs = [None, None, torch.empty(B, dtype=torch.int32, device=x.device), torch.empty(B, **f32)]
             outs += [torch.empty(B, self.G, **f32)] if n_out == 5 else []
         else:
             outs = [torch.empty(B, **f32), torch.empty_like(x)] + [None] * (n_out - 2)
-        return name, need, args + tuple(p(t) for t in outs), outs
+        return name, need, args + tuple(_ptr(t) for t in outs), outs
 
     def _launch(self, x, var, fit=False):
         """One call of the C entry on x (f32, contiguous): (best, rmsd[, group_rmsd]) when `fit`, else (logp, grad)."""
-        import ctypes as C
         name, need, args, outs = self._entry(x, var, fit)
-        if need > self._work.numel():
-            self._work = torch.empty(need, dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = getattr(self.lib, name)(*args, C.c_void_p(self._work.data_ptr() if need else 0), self._work.numel())
-        if rc != 0:
-            from . import capi
-            raise capi.GenieError('%s failed (%d)' % (name, rc))
+        self._call(name, *args, *self._workspace(need))
         return tuple(t for t in outs if t is not None)
 
 
@@ -689,20 +687,7 @@ def restraint_table(restraints, n_res):
     return (torch.tensor(offset, dtype=torch.int32), torch.tensor([e[1] for e in entries], dtype=torch.int32), f32(2), f32(3), f32(4))
 
 
-class _ShapePotentialFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x0, pot, var):
-        logp, grad = pot._launch(pot._checked(x0), var)
-        ctx.save_for_backward(grad)
-        return logp
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        grad, = ctx.saved_tensors
-        return grad_output[:, None, None] * grad, None, None
-
-
-class ShapePotential:
+class ShapePotential(_HipPotential):
     """Shape guidance as one HIP pass (genie_shape_potential, csrc/shape_kernels.hip; include/genie_hip.h states the mathematics):
     `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside MotifPotential
     (SumPotential adds them).  Three terms, each a squared hinge in Angstrom:
@@ -726,7 +711,6 @@ class ShapePotential:
     def __init__(self, n_res, alphas_cumprod, rog_max=None, rog_weight=1.0, clash_distance=None, clash_separation=2, clash_weight=1.0,
                  restraints=None, tausq=1.0, device='cuda'):
         import math
-        from . import capi
         self.n_res = int(n_res)
         if self.n_res < 1:
             raise ValueError('n_res must be at least 1, got %r' % (n_res,))
@@ -742,62 +726,28 @@ class ShapePotential:
         # a term that is off is a weight of 0 to the entry
         self.rog_max, self.rog_weight = (0.0, 0.0) if rog_max is None else (float(rog_max), float(rog_weight))
         self.clash_distance, self.clash_weight = (0.0, 0.0) if clash_distance is None else (float(clash_distance), float(clash_weight))
-        self.clash_separation, self.tausq = int(clash_separation), float(tausq)
+        self.clash_separation = int(clash_separation)
         self.restraints = check_restraints(restraints or [], self.n_res)
         table = restraint_table(self.restraints, self.n_res)
-        self.lib = capi.load_library()
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise capi.GenieError('ShapePotential runs on the GPU (libgenie_hip); there is no CPU path')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        super().__init__(n_res, alphas_cumprod, tausq, device)
         self.R2 = int(table[1].numel())
         self.table = tuple(t.to(self.device) for t in table) if self.R2 else (None,) * 5
-        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
-        self._work = torch.zeros(0, dtype=torch.float32, device=self.device)
-        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-
-    def variance(self, step):
-        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
-
-    def __call__(self, x0, step):
-        return _ShapePotentialFn.apply(x0, self, self.variance(step))
 
     def describe(self, x):
         """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
-        from . import capi
         report, = self._launch(self._checked(x), self._one, report=True)                   # (the energies do not depend on var)
-        counts = ('n_clash', 'n_violated')
-        return {k: report[:, i].round().long() if k in counts else report[:, i].clone() for i, k in enumerate(capi.SHAPE_REPORT)}
-
-    def _checked(self, x0):
-        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
-            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
-        if x0.device != self.device:
-            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
-        return x0.detach().to(torch.float32).contiguous()
+        return _decode_report(report, capi.SHAPE_REPORT, ('n_clash', 'n_violated'))
 
     def _launch(self, x, var, report=False):
         """One call of the C entry on x (f32, contiguous): (report [B, 8],) when `report`, else (logp, grad)."""
-        import ctypes as C
-        from . import capi
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
         B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
         if report:
             outs = [None, None, torch.empty(B, len(capi.SHAPE_REPORT), **f32)]
         else:
             outs = [torch.empty(B, **f32), torch.empty_like(x), None]
-        need = self.lib.genie_shape_potential_work_bytes(B, self.n_res)
-        if need > self._work.numel() * 4:
-            self._work = torch.empty(need // 4, **f32)
-        with torch.cuda.device(x.device):
-            rc = self.lib.genie_shape_potential(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
-                                                self.rog_max, self.rog_weight, self.clash_distance, self.clash_separation,
-                                                self.clash_weight, self.R2, *(p(t) for t in self.table), p(var),
-                                                *(p(t) for t in outs), p(self._work), self._work.numel() * 4)
-        if rc != 0:
-            msg = self.lib.genie_last_error(None)
-            raise capi.GenieError('genie_shape_potential failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        self._call('genie_shape_potential', self._stream(), B, self.n_res, _ptr(x), self.rog_max, self.rog_weight, self.clash_distance,
+                   self.clash_separation, self.clash_weight, self.R2, *(_ptr(t) for t in self.table), _ptr(var), *(_ptr(t) for t in outs),
+                   *self._workspace(self.lib.genie_shape_potential_work_bytes(B, self.n_res)))
         return tuple(t for t in outs if t is not None)
 
 
@@ -835,20 +785,7 @@ def ss_string(codes):
     return ''.join(SS_LETTERS[int(c)] for c in codes)
 
 
-class _SecStructPotentialFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x0, pot, var):
-        logp, grad = pot._launch(pot._checked(x0), var)
-        ctx.save_for_backward(grad)
-        return logp
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        grad, = ctx.saved_tensors
-        return grad_output[:, None, None] * grad, None, None
-
-
-class SecStructPotential:
+class SecStructPotential(_HipPotential):
     """Secondary-structure guidance as one HIP pass (genie_secstruct_potential, csrc/secstruct_kernels.hip; include/genie_hip.h
     states the mathematics): `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for
     TwistedSampler beside MotifPotential and ShapePotential (SumPotential adds them).  Every five-residue window is scored against a
@@ -876,9 +813,7 @@ class SecStructPotential:
 
     def __init__(self, n_res, alphas_cumprod, helix=None, helix_weight=1.0, extended=None, extended_weight=1.0, target=None,
                  target_weight=1.0, table=None, tausq=1.0, device='cuda'):
-        import ctypes as C
         import math
-        from . import capi
         self.n_res = int(n_res)
         if self.n_res < 5:
             raise ValueError('n_res must be at least 5 (a window covers five residues), got %r' % (n_res,))
@@ -919,60 +854,30 @@ class SecStructPotential:
         self.helix, self.helix_weight = ((0.0, 1.0), 0.0) if bounds['helix'] is None else (bounds['helix'], float(helix_weight))
         self.extended, self.extended_weight = ((0.0, 1.0), 0.0) if bounds['extended'] is None else (bounds['extended'], float(extended_weight))
         self.target, self.target_weight = target, (0.0 if target is None else float(target_weight))
-        self.table, self.tausq = table, float(tausq)
+        self.table = table
         self._table = (C.c_float * 16)(*table)
-        self.lib = capi.load_library()
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise capi.GenieError('SecStructPotential runs on the GPU (libgenie_hip); there is no CPU path')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
+        super().__init__(n_res, alphas_cumprod, tausq, device)
         self.target_t = None if target is None else torch.tensor([SS_CODES[c] for c in target], dtype=torch.int8).to(self.device)
-        self.abar = torch.as_tensor(alphas_cumprod).to(self.device)
-        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-
-    def variance(self, step):
-        return xstart_variance(self.abar[step], self.tausq).to(torch.float32).reshape(1).contiguous()
-
-    def __call__(self, x0, step):
-        return _SecStructPotentialFn.apply(x0, self, self.variance(step))
 
     def describe(self, x):
         """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
-        from . import capi
         report, _ = self._launch(self._checked(x), self._one, report=True)                 # (the energies do not depend on var)
-        counts = ('n_helix', 'n_extended', 'n_target_missed')
-        return {k: report[:, i].round().long() if k in counts else report[:, i].clone() for i, k in enumerate(capi.SECSTRUCT_REPORT)}
+        return _decode_report(report, capi.SECSTRUCT_REPORT, ('n_helix', 'n_extended', 'n_target_missed'))
 
     def assign(self, x):
         """The hard assignment of every sample of x [B,N,3]: int8 [B, N], 0 C, 1 H, 2 E, on the potential's device."""
         return self._launch(self._checked(x), self._one, report=True)[1]
 
-    def _checked(self, x0):
-        if x0.dim() != 3 or x0.shape[1] != self.n_res or x0.shape[2] != 3:
-            raise ValueError('x0 must be [B, %d, 3], got %s' % (self.n_res, tuple(x0.shape)))
-        if x0.device != self.device:
-            raise ValueError('x0 is on %s, the potential on %s' % (x0.device, self.device))
-        return x0.detach().to(torch.float32).contiguous()
-
     def _launch(self, x, var, report=False):
         """One call of the C entry on x (f32, contiguous): (report [B, 8], assignment [B, N]) when `report`, else (logp, grad)."""
-        import ctypes as C
-        from . import capi
-        p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
         B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
         if report:
             outs = [None, None, torch.empty(B, len(capi.SECSTRUCT_REPORT), **f32), torch.empty(B, self.n_res, dtype=torch.int8, device=x.device)]
         else:
             outs = [torch.empty(B, **f32), torch.empty_like(x), None, None]
-        with torch.cuda.device(x.device):
-            rc = self.lib.genie_secstruct_potential(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), B, self.n_res, p(x),
-                                                    self._table, self.helix[0], self.helix[1], self.helix_weight, self.extended[0],
-                                                    self.extended[1], self.extended_weight, p(self.target_t), self.target_weight,
-                                                    p(var), *(p(t) for t in outs))
-        if rc != 0:
-            msg = self.lib.genie_last_error(None)
-            raise capi.GenieError('genie_secstruct_potential failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        self._call('genie_secstruct_potential', self._stream(), B, self.n_res, _ptr(x), self._table, self.helix[0], self.helix[1],
+                   self.helix_weight, self.extended[0], self.extended[1], self.extended_weight, _ptr(self.target_t), self.target_weight,
+                   _ptr(var), *(_ptr(t) for t in outs))
         return tuple(t for t in outs if t is not None)
 
 

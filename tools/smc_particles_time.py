@@ -22,33 +22,18 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 
 def systems_step(ctx, twist, S, K, reweight, state, alpha=0.012, scale=1.0, ess_fraction=0.5):
-    """One iteration of TwistedSampler._sample_systems' loop body (genie2_amd/smc.py) at ctx['step'], the state left unchanged."""
+    """One iteration of TwistedSampler._sample's loop with num_particles (genie2_amd/smc.py: guided_step, then one SmcReweight call)
+    at ctx['step'], the state left unchanged."""
     import torch
-    eng, sched, step, B, trans, rots = ctx['eng'], ctx['sched'], ctx['step'], ctx['B'], ctx['trans'], ctx['rots']
-    N = ctx['N']
-    abar, betas = sched['alphas_cumprod'], sched['betas']
-    ts = torch.full((B,), step, dtype=torch.int32, device=trans.device)
-    c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
-    z = eng.denoise(trans, rots, ts)['z']
-    x0 = ((trans - c1 * z) / c0).detach().requires_grad_(True)
-    log_prob = twist(x0, step)
-    g = torch.autograd.grad(log_prob.mean(), x0)[0] * B
-    _, dz_part = eng.denoise_vjp(ctx['w'], trans, rots, ts, (-c1 / c0) * g)
-    grad = g / c0 + dz_part
-    norm = grad.double().view(S, -1).norm(dim=1).float().view(S, 1, 1, 1)
-    grad = (grad.view(S, K, N, 3) * alpha * norm / (alpha + norm)).view(B, N, 3)
-    x0u = x0.detach()
-    x0t = x0u + grad
-    coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
-    coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
-    mean_t, mean_u = coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans
-    sigma = sched['sqrt_betas'][step]
+    import smc_step_time as base
+    from genie2_amd.smc import guided_step
+    mean_t, mean_u, sigma, log_prob = guided_step(base.guided_state(ctx, twist, S, alpha), 0, ctx['step'], ctx['trans'], ctx['rots'])
     new = (mean_t + scale * sigma * ctx['noise']) * ctx['mask']
-    u = torch.rand(S, device=trans.device) / K
+    u = torch.rand(S, device=ctx['trans'].device) / K
     state['log_proposal'].zero_()
     state['log_w_acc'].zero_()
-    x_out, _ = reweight(new, mean_t, mean_u, sigma, log_prob.detach(), u, ess_fraction, state['log_proposal'], state['log_w_acc'])
-    return eng.frenet(x_out)
+    x_out, _ = reweight(new, mean_t, mean_u, sigma, log_prob, u, ess_fraction, state['log_proposal'], state['log_w_acc'])
+    return ctx['eng'].frenet(x_out)
 
 
 def median_step_ms(fn, batches, steps, warmup):

@@ -66,34 +66,23 @@ def potential_call(ctx, twist):
     return torch.autograd.grad(lp.mean(), x0)[0]
 
 
+def guided_state(ctx, twist, S=None, alpha=0.012):
+    """What genie2_amd.smc.guided_step reads of a sampler's state, from `ctx`: the full schedule, every step guided."""
+    import types
+    return types.SimpleNamespace(eng=ctx['eng'], w=ctx['w'], sched=ctx['sched'], tw_coef=None, twist=twist, alpha=alpha, unguided=0, S=S)
+
+
 def twisted_step(ctx, twist, alpha=0.012, scale=1.0):
-    """One iteration of TwistedSampler._sample's loop body (genie2_amd/smc.py) at ctx['step'], the state left unchanged."""
-    import torch
-    from genie2_amd.smc import compute_ess_from_log_w, log_normal_density
-    eng, sched, step, B, trans, rots = ctx['eng'], ctx['sched'], ctx['step'], ctx['B'], ctx['trans'], ctx['rots']
-    abar, betas = sched['alphas_cumprod'], sched['betas']
-    ts = torch.full((B,), step, dtype=torch.int32, device=trans.device)
-    c0, c1 = torch.sqrt(abar[step]), torch.sqrt(1 - abar[step])
-    z = eng.denoise(trans, rots, ts)['z']
-    x0 = ((trans - c1 * z) / c0).detach().requires_grad_(True)
-    log_prob = twist(x0, step)
-    g = torch.autograd.grad(log_prob.mean(), x0)[0] * B
-    _, dz_part = eng.denoise_vjp(ctx['w'], trans, rots, ts, (-c1 / c0) * g)
-    grad = g / c0 + dz_part
-    norm = grad.double().norm().float()
-    grad = grad * alpha * norm / (alpha + norm)
-    x0u = x0.detach()
-    x0t = x0u + grad
-    coef1 = torch.sqrt(abar[step - 1]) * betas[step] / (1 - abar[step])
-    coef2 = sched['sqrt_alphas'][step] * (1.0 - abar[step - 1]) / (1 - abar[step])
-    mean_t, mean_u = coef1 * x0t + coef2 * trans, coef1 * x0u + coef2 * trans
-    sigma = sched['sqrt_betas'][step]
+    """One iteration of TwistedSampler._sample's loop for one system (genie2_amd/smc.py: guided_step, then the weights and the ESS
+    read of _host_update) at ctx['step'], the state left unchanged."""
+    from genie2_amd.smc import compute_ess_from_log_w, guided_step, log_normal_density
+    mean_t, mean_u, sigma, log_prob = guided_step(guided_state(ctx, twist, None, alpha), 0, ctx['step'], ctx['trans'], ctx['rots'])
     new = (mean_t + scale * sigma * ctx['noise']) * ctx['mask']
     log_rev = log_normal_density(new, mean_u, sigma ** 2).sum(dim=(1, 2))
     log_tw = log_normal_density(new, mean_t, sigma ** 2).sum(dim=(1, 2))
-    log_w = log_rev + log_prob.detach() - log_tw
+    log_w = log_rev + log_prob - log_tw
     float(compute_ess_from_log_w(log_w))                     # the sampler's per-step host read (ess_trace)
-    return eng.frenet(new)
+    return ctx['eng'].frenet(new)
 
 
 def time_ms(fn, reps, warmup):
