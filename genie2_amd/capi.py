@@ -114,6 +114,9 @@ SYMBOLS = {
     'genie_shape_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'genie_secstruct_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_float] * 6 +
                                   [C.c_void_p, C.c_float] + [C.c_void_p] * 5),
+    'genie_sheet_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_float] * 6 +
+                              [C.c_int] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 6 + [C.c_size_t]),
+    'genie_sheet_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -123,6 +126,14 @@ SECSTRUCT_REPORT = ('helix_content', 'extended_content', 'n_helix', 'n_extended'
                     'n_target_missed')      # GENIE_SECSTRUCT_REPORT slots
 # P-SEA's C-alpha criteria (Labesse et al. 1997) for d2, d3, d4 and chi from ideal coordinates: H mu, H sigma, E mu, E sigma
 SECSTRUCT_TABLE = (5.5, 5.3, 6.4, 0.77, 0.5, 0.5, 0.6, 0.25, 6.7, 9.9, 12.4, -0.12, 0.6, 0.9, 1.1, 0.45)
+
+SHEET_REPORT = ('antiparallel_content', 'parallel_content', 'n_antiparallel', 'n_parallel', 'n_paired', 'e_antiparallel', 'e_parallel',
+                'e_ladder', 'n_ladder_missed')      # GENIE_SHEET_REPORT slots
+SHEET_COUNTS = ('n_antiparallel', 'n_parallel', 'n_paired', 'n_ladder_missed')
+# ideal pleated-sheet geometry: mu_A, sigma_A, mu_P, sigma_P in Angstrom (neighbouring strands 4.8 A apart; antiparallel C-alpha pairs
+# alternate around 4.5 / 5.5 A)
+SHEET_TABLE = (5.0, 0.6, 4.8, 0.5)
+SHEET_PARALLEL, SHEET_RUNG = 1 << 29, 1 << 30       # GENIE_SHEET_PARALLEL, GENIE_SHEET_RUNG: flags of a ladder table's partner words
 
 _lib = None
 

@@ -32,12 +32,17 @@ skipped.
 `--helix_min` / `--helix_max`, `--extended_min` / `--extended_max` and `--ss_target` (with their weights and `--ss_tausq`: the flags
 of add_secstruct_arguments in the same module) add secondary-structure guidance: the potentials asked for are summed in the order
 motif, shape, secondary structure, `--write_secstruct` writes outdir/secstruct/{length}_{index}.txt as that CLI does, and lengths
-other than the blueprint's are skipped."""
+other than the blueprint's are skipped.
+
+`--antiparallel_min` / `--antiparallel_max`, `--parallel_min` / `--parallel_max` and `--ladder_file` (with their weights and
+`--sheet_tausq`: the flags of add_sheet_arguments in the same module) add strand-pairing guidance, summed last; `--write_sheet` writes
+outdir/sheet/{length}_{index}.txt as that CLI does, and lengths that cannot hold the ladder are skipped."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import GuidedRunner, add_guidance_arguments, add_secstruct_arguments, add_shape_arguments
+from .sample_unconditional_shape import (GuidedRunner, add_guidance_arguments, add_secstruct_arguments, add_shape_arguments,
+                                         add_sheet_arguments)
 
 
 def load_motif_segments(filepath):
@@ -132,6 +137,7 @@ def build_parser():
     add_guidance_arguments(p, ' (an addition to the reference CLI, like --align)', 'num_steps', 'num_particles')
     add_shape_arguments(p)
     add_secstruct_arguments(p)
+    add_sheet_arguments(p)
     return p
 
 

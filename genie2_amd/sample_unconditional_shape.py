@@ -2,7 +2,7 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure term (below), is needed.
+least one of the three, or a secondary-structure or sheet term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -14,13 +14,21 @@ structure: rog, min_distance, n_clash, e_rog, e_clash, e_restraint, n_violated, 
 length - 4 five-residue windows) in a range, and `--ss_target STRING|FILE` pulls residues to a blueprint over `H`, `E` and `-` (or `C`:
 free; in a file whitespace is ignored and `#` starts a comment): a SecStructPotential (csrc/secstruct_kernels.hip), summed with the
 shape terms when both are asked for and enough on its own.  Giving only one of min / max leaves the other at 0 / 1.  "Extended" is
-local geometry only, with no strand pairing.  A length other than the blueprint's is skipped.  `--write_secstruct` adds
-outdir/secstruct/{length}_{index}.txt: the hard assignment of the written structure as a string over `HEC`, then one `key value` line
-per field of SecStructPotential.describe.
+local geometry only, with no strand pairing (the sheet terms below add it).  A length other than the blueprint's is skipped.
+`--write_secstruct` adds outdir/secstruct/{length}_{index}.txt: the hard assignment of the written structure as a string over `HEC`,
+then one `key value` line per field of SecStructPotential.describe.
+
+`--antiparallel_min` / `--antiparallel_max` and `--parallel_min` / `--parallel_max` keep the soft antiparallel / parallel strand-pairing
+content (rungs per residue; an interior strand of a large sheet approaches 1) in a range, and `--ladder_file FILE` pulls listed rungs
+together: a SheetPotential (csrc/sheet_kernels.hip), summed after the others and enough on its own.  Giving only a max leaves the min
+at 0, only a min leaves the content unbounded above.  The ladder file has one ladder per line, `i j len A|P [weight]`: residues 0-based,
+class A pairs i + k with j - k, class P pairs i + k with j + k, k = 0..len-1; `#` starts a comment.  A length that cannot hold the
+ladder is skipped.  `--write_sheet` adds outdir/sheet/{length}_{index}.txt: one `i j A|P` line per formed rung of the written
+structure (each rung once, i < j), then one `key value` line per field of SheetPotential.describe.
 
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
-add_shape_arguments and add_secstruct_arguments too and then guides with the sum of the potentials asked for."""
+add_shape_arguments, add_secstruct_arguments and add_sheet_arguments too and then guides with the sum of the potentials asked for."""
 import os
 
 from tqdm import tqdm
@@ -31,6 +39,7 @@ SHAPE_KEYS = ('rog_max', 'rog_weight', 'clash_distance', 'clash_separation', 'cl
 COUNTS = ('n_clash', 'n_violated')
 SECSTRUCT_KEYS = ('helix_weight', 'extended_weight', 'ss_target_weight', 'ss_tausq')
 SECSTRUCT_COUNTS = ('n_helix', 'n_extended', 'n_target_missed')
+SHEET_KEYS = ('antiparallel_weight', 'parallel_weight', 'ladder_weight', 'sheet_tausq')
 
 
 def add_shape_arguments(parser):
@@ -87,12 +96,13 @@ def shape_potential(constants, length, abar, device):
 
 
 def write_report(report, counts, directory, length, offset, headers=None):
-    """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: the line headers[i] when
-    there are headers, then a `key value` line per field of `report`, %d for the fields named in `counts`, %.3f for the others."""
+    """One file per sample of a batch (so worker processes never share one), {length}_{offset + i}.txt: the line(s) headers[i] when
+    there are headers (nothing for an empty one), then a `key value` line per field of `report`, %d for the fields named in `counts`,
+    %.3f for the others."""
     os.makedirs(directory, exist_ok=True)
     for i in range(len(next(iter(report.values())))):
         with open(os.path.join(directory, '{}_{}.txt'.format(length, offset + i)), 'w') as fh:
-            if headers is not None:
+            if headers is not None and headers[i]:
                 fh.write(headers[i] + '\n')
             for key, column in report.items():
                 fh.write(('{} {:d}\n' if key in counts else '{} {:.3f}\n').format(key, column[i].item()))
@@ -105,7 +115,8 @@ def write_shape_report(last_shape, directory, length, offset):
 
 def add_secstruct_arguments(parser):
     tail = ' (an addition to the reference CLI, like --rog_max)'
-    for name, word in (('helix', 'helix'), ('extended', 'extended (strand-like, local geometry only)')):
+    for name, word in (('helix', 'helix'),
+                       ('extended', 'extended (strand-like, local geometry only: the sheet flags guide strand pairing)')):
         parser.add_argument('--%s_min' % name, type=float, default=None,
                             help='Guide the soft %s content, a fraction of the five-residue windows, above this; default: no such '
                                  'bound' % word + tail)
@@ -162,6 +173,83 @@ def secstruct_potential(constants, length, abar, device):
                               tausq=constants['ss_tausq'], device=device)
 
 
+def add_sheet_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    for name in ('antiparallel', 'parallel'):
+        parser.add_argument('--%s_min' % name, type=float, default=None,
+                            help='Guide the soft %s strand-pairing content, in rungs per residue, above this; default: no such '
+                                 'bound' % name + tail)
+        parser.add_argument('--%s_max' % name, type=float, default=None,
+                            help='Guide the soft %s strand-pairing content below this many rungs per residue; default: no such '
+                                 'bound' % name + tail)
+        parser.add_argument('--%s_weight' % name, type=float, default=1.0, help='Weight of the %s content term' % name + tail)
+    parser.add_argument('--ladder_file', type=str, default=None,
+                        help='Rungs to pull together, one `i j len A|P [weight]` line per ladder (0-based residues; A pairs i + k with '
+                             'j - k, P with j + k)' + tail)
+    parser.add_argument('--ladder_weight', type=float, default=1.0, help='Weight of the ladder term' + tail)
+    parser.add_argument('--sheet_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the sheet terms, Angstrom^2' + tail)
+    parser.add_argument('--write_sheet', action='store_true',
+                        help='Write outdir/sheet/{length}_{index}.txt: the formed rungs, soft contents, counts and energies of every '
+                             'written structure' + tail)
+
+
+def sheet_constants(params):
+    """The sheet keys of a runner's constants: the flags of add_sheet_arguments, each min / max pair as 'antiparallel' / 'parallel' =
+    (min, max) or None (one of the two given: the other is 0 / inf), the ladder file read into 'ladder'."""
+    import math
+    from .smc import load_ladder
+    defaults = dict(antiparallel_weight=1.0, parallel_weight=1.0, ladder_weight=1.0, sheet_tausq=1.0)
+    c = {k: params.get(k, defaults[k]) for k in SHEET_KEYS}
+    for name in ('antiparallel', 'parallel'):
+        lo, hi = params.get(name + '_min'), params.get(name + '_max')
+        c[name] = None if lo is None and hi is None else (0.0 if lo is None else lo, math.inf if hi is None else hi)
+    c['ladder'] = load_ladder(params['ladder_file']) if params.get('ladder_file') else []
+    c['write_sheet'] = bool(params.get('write_sheet', False))
+    return c
+
+
+def has_sheet_terms(constants):
+    return constants.get('antiparallel') is not None or constants.get('parallel') is not None or bool(constants.get('ladder'))
+
+
+def ladder_lengths(tasks, ladder):
+    """The tasks long enough to hold every rung of the ladder (its highest centre is at most length - 2: check_ladder's rule); the
+    others are skipped with one printed line."""
+    top = max([max(i + n - 1, j if cls == 'A' else j + n - 1) for i, j, n, cls, *_ in ladder], default=-2)
+    need = top + 2
+    short = [t['length'] for t in tasks if t['length'] < need]
+    if short:
+        print('skipping lengths shorter than the {} residues the ladder needs: {}'.format(need, ', '.join(map(str, short))))
+    return [t for t in tasks if t['length'] >= need]
+
+
+def sheet_potential(constants, length, abar, device):
+    """The SheetPotential the constants ask for at this length, or None when they ask for no term.  (Lengths that cannot hold the
+    ladder never get here: ladder_lengths drops them when the tasks are made.)"""
+    if not has_sheet_terms(constants):
+        return None
+    from .smc import SheetPotential
+    return SheetPotential(length, abar, antiparallel=constants['antiparallel'], antiparallel_weight=constants['antiparallel_weight'],
+                          parallel=constants['parallel'], parallel_weight=constants['parallel_weight'],
+                          ladder=constants['ladder'] or None, ladder_weight=constants['ladder_weight'],
+                          tausq=constants['sheet_tausq'], device=device)
+
+
+def formed_rungs(pairs):
+    """One row of TwistedSampler.last_pairs ([N, 2] partners) -> the lines `i j A|P` of its formed rungs, each once with i < j,
+    class A first, ascending.  (A residue names only its best partner per class; a rung is listed when either end names the other.)"""
+    rows = pairs.tolist()
+    found = sorted({(c, min(n, m), max(n, m)) for n, row in enumerate(rows) for c, m in enumerate(row) if m >= 0})
+    return ['{} {} {}'.format(i, j, 'AP'[c]) for c, i, j in found]
+
+
+def write_sheet_report(pairs, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a line `i j A|P` per formed rung of TwistedSampler.last_pairs, then
+    a `key value` line per field of `report` (the sheet fields of last_shape), %.3f for contents and energies, %d for counts."""
+    from .capi import SHEET_COUNTS
+    write_report(report, SHEET_COUNTS, directory, length, offset, ['\n'.join(formed_rungs(row)) for row in pairs])
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -206,12 +294,13 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape and secondary-structure potentials the constants ask for, in that
-    order; `after_batch` writes a subclass's own reports."""
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure and sheet potentials the constants ask for, in
+    that order; `after_batch` writes a subclass's own reports."""
 
     def guided_lengths(self, tasks, params):
-        """The tasks whose length the restraints and the blueprint allow."""
-        return target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
+        """The tasks whose length the restraints, the blueprint and the ladder allow."""
+        tasks = target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
+        return ladder_lengths(tasks, sheet_constants(params)['ladder'])
 
     def create_tasks(self, params):
         return self.guided_lengths(super().create_tasks(params), params)
@@ -222,6 +311,7 @@ class GuidedRunner(UnconditionalRunner):
         c['num_particles'] = params.get('num_particles')
         c.update(shape_constants(params))
         c.update(secstruct_constants(params))
+        c.update(sheet_constants(params))
         return c
 
     def batch_potentials(self, constants, length, abar, device):
@@ -242,11 +332,12 @@ class GuidedRunner(UnconditionalRunner):
             length, outdir = task['length'], constants['outdir']
             shape = shape_potential(constants, length, abar, device)
             secstruct = secstruct_potential(constants, length, abar, device)
+            sheet = sheet_potential(constants, length, abar, device)
             for batch, offset in self.batches(constants, outdir, length):
                 sampler.sample({
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
-                    'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct),
+                    'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **self.partial_params(constants)})
@@ -259,14 +350,18 @@ class GuidedRunner(UnconditionalRunner):
                 if constants['write_secstruct'] and secstruct is not None:
                     write_secstruct_report(sampler.last_secstruct, report_fields(sampler.last_shape, capi.SECSTRUCT_REPORT),
                                            os.path.join(outdir, 'secstruct'), length, offset)
+                if constants['write_sheet'] and sheet is not None:
+                    write_sheet_report(sampler.last_pairs, report_fields(sampler.last_shape, capi.SHEET_REPORT),
+                                       os.path.join(outdir, 'sheet'), length, offset)
 
 
 class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
-        if not has_shape_terms(c) and not has_secstruct_terms(c):
-            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, or a secondary-structure '
-                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target)')
+        if not has_shape_terms(c) and not has_secstruct_terms(c) and not has_sheet_terms(c):
+            raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
+                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target) or a sheet term '
+                             '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file)')
         return c
 
 
@@ -276,6 +371,7 @@ def build_parser():
     add_guidance_arguments(p, '', 'resume', 'guidance_alpha', 'ess_threshold', 'last_unguided_steps', 'num_steps', 'num_particles')
     add_shape_arguments(p)
     add_secstruct_arguments(p)
+    add_sheet_arguments(p)
     return p
 
 

@@ -6,7 +6,8 @@ does); the reference's potential acts on a [B, N, 3] tensor and stays in PyTorch
 MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).  ShapePotential (csrc/shape_kernels.hip: radius of
 gyration, clashes, distance restraints; not in the reference) is the second built-in potential, SecStructPotential
 (csrc/secstruct_kernels.hip: helix / extended content and a blueprint; the reference's sampler/secstruct.py runs P-SEA on the host and
-is not differentiable) the third, and SumPotential adds potentials.
+is not differentiable) the third, SheetPotential (csrc/sheet_kernels.hip: antiparallel / parallel strand pairing and a ladder of listed
+rungs; not in the reference) the fourth, and SumPotential adds potentials.
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -132,9 +133,11 @@ class TwistedSampler(UnconditionalSampler):
     'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample; with motif groups also 'group_rmsd' and the 'groups' labels),
     or None when it has no `locate`; `last_shape` what its `describe` says of them (ShapePotential.describe: 'rog', 'min_distance',
     'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation' as CPU tensors, one row per returned sample; with a
-    SecStructPotential its eight fields, and with a SumPotential every member's), or None when it has no `describe`; `last_secstruct`
+    SecStructPotential its eight fields, with a SheetPotential its nine, and with a SumPotential every member's), or None when it
+    has no `describe`; `last_secstruct`
     what its `assign` says of them (SecStructPotential.assign: int8 [rows, N] on the CPU, 0 C, 1 H, 2 E), or None when it has no
-    `assign`.
+    `assign`; `last_pairs` what its `pairs` says of them (SheetPotential.pairs: int32 [rows, N, 2] on the CPU, every residue's
+    antiparallel and parallel partner, -1 for none), or None when it has no `pairs`.
     Optional 'num_steps' = K (not in the reference) visits the K timesteps of pack.respaced_steps with the ancestral kernel between
     them (pack.twisted_coefficients): `ess_trace` then has K - 1 entries, the last visited step takes the role of step 1, and
     `last_unguided_steps` and the potential keep reading the timestep itself.  'sampler': 'ddim' is refused (ValueError): the
@@ -241,6 +244,7 @@ class TwistedSampler(UnconditionalSampler):
             self.last_fit = {k: v.cpu() if torch.is_tensor(v) else v for k, v in twist.locate(trans).items()}
         self.last_shape = {k: v.cpu() for k, v in twist.describe(trans).items()} if hasattr(twist, 'describe') else None
         self.last_secstruct = twist.assign(trans).cpu() if hasattr(twist, 'assign') else None
+        self.last_pairs = twist.pairs(trans).cpu() if hasattr(twist, 'pairs') else None
         feats['atom_positions'] = trans.cpu()
         self.last_start_rmsd = None if start is None else start_rmsd(feats['atom_positions'], start, feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
@@ -808,8 +812,9 @@ class SecStructPotential(_HipPotential):
     `assign(x)` is the hard assignment, int8 [B, N] with 0 C, 1 H, 2 E.
 
     "Extended" is local geometry only: there is no strand pairing (P-SEA's inter-strand criteria are out of scope), so it says that a
-    stretch is straight and flat like a strand, not that it sits in a sheet.  The defaults (the table, weights 1, tausq = 1 A^2, the
-    rational score) are design choices: no trained checkpoint is in the tree, so their effect on sample quality is unmeasured."""
+    stretch is straight and flat like a strand, not that it sits in a sheet: SheetPotential, below, scores pairing.  The defaults
+    (the table, weights 1, tausq = 1 A^2, the rational score) are design choices: no trained checkpoint is in the tree, so their
+    effect on sample quality is unmeasured."""
 
     def __init__(self, n_res, alphas_cumprod, helix=None, helix_weight=1.0, extended=None, extended_weight=1.0, target=None,
                  target_weight=1.0, table=None, tausq=1.0, device='cuda'):
@@ -881,12 +886,204 @@ class SecStructPotential(_HipPotential):
         return tuple(t for t in outs if t is not None)
 
 
+def load_ladder(path):
+    """A ladder file -> [(i, j, len, cls, weight), ...] for SheetPotential: one ladder per line, `i j len A|P [weight]`, residues
+    0-based like the motif_locations files: class A pairs residue i + k with j - k, class P pairs i + k with j + k, k = 0..len-1;
+    weight 1 when omitted; `#` starts a comment, blank lines are ignored.  A bad line raises ValueError('<path>:<line number>: ...')."""
+    out = []
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            fields = line.split('#', 1)[0].split()
+            if not fields:
+                continue
+            if len(fields) not in (4, 5):
+                raise ValueError('%s:%d: expected `i j len A|P [weight]`, got %d fields' % (path, number, len(fields)))
+            try:
+                i, j, n = int(fields[0]), int(fields[1]), int(fields[2])
+                weight = float(fields[4]) if len(fields) == 5 else 1.0
+            except ValueError:
+                raise ValueError('%s:%d: residues and len are integers, weight a number: %r' % (path, number, line.strip())) from None
+            if fields[3] not in ('A', 'P'):
+                raise ValueError('%s:%d: the class is A or P, got %r' % (path, number, fields[3]))
+            out.append((i, j, n, fields[3], weight))
+    return out
+
+
+def check_ladder(ladder, n_res):
+    """The ladder of SheetPotential, validated on the host: [(i, j, len, 'A'|'P'[, weight]), ...] -> its rungs [(i, j, cls, weight),
+    ...] with i < j, in the order given.  Every rung's two centres lie in 1..n_res-2 and at least 3 apart, len >= 1, weight finite and
+    >= 0 (1 when omitted), no rung listed twice in one class."""
+    import math
+    out, seen = [], set()
+    for k, e in enumerate(ladder):
+        e = tuple(e)
+        if len(e) not in (4, 5):
+            raise ValueError("ladder %d: expected (i, j, len, 'A'|'P'[, weight]), got %r" % (k, e))
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in e[:3]):
+            raise ValueError('ladder %d: residues and len must be integers, got %r' % (k, e[:3]))
+        i, j, n, cls, weight = int(e[0]), int(e[1]), int(e[2]), e[3], float(e[4]) if len(e) == 5 else 1.0
+        if cls not in ('A', 'P'):
+            raise ValueError("ladder %d: the class must be 'A' or 'P', got %r" % (k, cls))
+        if n < 1:
+            raise ValueError('ladder %d: len must be at least 1, got %d' % (k, n))
+        if not (math.isfinite(weight) and weight >= 0):
+            raise ValueError('ladder %d: the weight must be finite and >= 0, got %r' % (k, weight))
+        for step in range(n):
+            a, b = i + step, (j - step if cls == 'A' else j + step)
+            a, b = min(a, b), max(a, b)
+            if not (1 <= a and b <= n_res - 2):
+                raise ValueError('ladder %d: the rung (%d, %d) needs both residues in 1..%d' % (k, a, b, n_res - 2))
+            if b - a < 3:
+                raise ValueError('ladder %d: the residues of the rung (%d, %d) are less than 3 apart' % (k, a, b))
+            if (a, b, cls) in seen:
+                raise ValueError('ladder %d: the rung (%d, %d) is listed twice in class %s' % (k, a, b, cls))
+            seen.add((a, b, cls))
+            out.append((a, b, cls, weight))
+    return out
+
+
+def ladder_table(rungs, n_res, table=None):
+    """The per-residue table genie_sheet_potential takes, as CPU tensors (offset int32 [n_res + 1], partner int32 [L2], mu, coef f32
+    [L2]), from check_ladder's rungs and the class table (mu_A, sigma_A, mu_P, sigma_P; capi.SHEET_TABLE by default): a rung's u is
+    a third of three squared deviations, so every rung gives three harmonic terms coef (d - mu)^2 with coef = weight / (3 sigma^2);
+    the terms of one class on one distance are merged; every term is listed at both of its residues, a residue's entries at
+    offset[n] .. offset[n + 1] - 1 with ascending partners (class A before P on one partner).  A partner word carries
+    capi.SHEET_PARALLEL for class P and capi.SHEET_RUNG where the term is the d0 of a listed rung."""
+    table = capi.SHEET_TABLE if table is None else table
+    terms = {}                                                      # (p, q, class index) -> [coef, is the d0 of a rung]
+    for i, j, cls, w in rungs:
+        c = 'AP'.index(cls)
+        ends = ((i, j), (i - 1, j + 1), (i + 1, j - 1)) if c == 0 else ((i, j), (i - 1, j - 1), (i + 1, j + 1))
+        for f, (p, q) in enumerate(ends):
+            t = terms.setdefault((p, q, c), [0.0, False])
+            t[0] += w / (3.0 * table[2 * c + 1] ** 2)
+            t[1] = t[1] or f == 0
+    entries = sorted([(p, q, c, v[0], v[1]) for (p, q, c), v in terms.items()] + [(q, p, c, v[0], v[1]) for (p, q, c), v in terms.items()])
+    offset = [0] * (n_res + 1)
+    for e in entries:
+        offset[e[0] + 1] += 1
+    for n in range(n_res):
+        offset[n + 1] += offset[n]
+    words = [e[1] | (capi.SHEET_PARALLEL if e[2] else 0) | (capi.SHEET_RUNG if e[4] else 0) for e in entries]
+    f32 = lambda values: torch.tensor(values, dtype=torch.float32)      # noqa: E731
+    return (torch.tensor(offset, dtype=torch.int32), torch.tensor(words, dtype=torch.int32), f32([table[2 * e[2]] for e in entries]),
+            f32([e[3] for e in entries]))
+
+
+class SheetPotential(_HipPotential):
+    """Sheet guidance as one HIP pass (genie_sheet_potential, csrc/sheet_kernels.hip; include/genie_hip.h states the mathematics):
+    `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside MotifPotential,
+    ShapePotential and SecStructPotential (SumPotential adds them).  It is the strand pairing SecStructPotential's "extended" class
+    does not have.  Every pair of interior residues at least `separation` apart is scored as an antiparallel and as a parallel rung
+    on three C-alpha distances (the pair and its two neighbouring pairs) with a squared-rational score in (0, 1]; the soft rung count
+    of a class is the sum of its scores.  Three terms:
+      antiparallel  (min, max) in rungs per residue (an interior strand of a large sheet approaches 1; max may be inf): the soft
+                    antiparallel count is kept between N min and N max by a squared hinge (None: off), weighted antiparallel_weight;
+      parallel      the same for the parallel class, weighted parallel_weight;
+      ladder        [(i, j, len, 'A'|'P'[, weight]), ...] (load_ladder reads them from a file): the listed rungs -- i + k with j - k
+                    for A, with j + k for P, k = 0..len-1 -- are pulled to their class harmonically, weighted ladder_weight.
+    log p = -(E_antiparallel + E_parallel + E_ladder) / (2 var), var = xstart_variance(alphas_cumprod[step], tausq) computed on the
+    device, so nothing on the per-step path reads device memory from the host; the forward keeps the gradient the kernel computes and
+    the backward scales it.  The likelihood is unnormalised.  `table` replaces the four class constants (capi.SHEET_TABLE: mu_A,
+    sigma_A, mu_P, sigma_P), `separation` the smallest j - i of an antiparallel and of a parallel rung (both at least 3; the default
+    5 for parallel keeps the (i, i+3) pairs of a helix out, which look parallel by C-alpha distance alone).
+
+    Everything is validated on the host before the device is looked at; a potential with no term enabled is a ValueError.
+    `describe(x)` reports every sample of x: 'antiparallel_content', 'parallel_content' (soft count / N), 'n_antiparallel',
+    'n_parallel' (formed rungs: all three distances within one sigma, int64), 'n_paired' (residues in a formed rung, int64),
+    'e_antiparallel', 'e_parallel', 'e_ladder' (the weighted energies, before the division by 2 var), 'n_ladder_missed' (listed rungs
+    that are not formed, int64), [B] tensors on the potential's device; `pairs(x)` is int32 [B, N, 2]: every residue's partner in its
+    best formed antiparallel (column 0) and parallel (column 1) rung, -1 for none.
+
+    The defaults (the table, the separations, weights 1, tausq = 1 A^2, the squared-rational score) are design choices from ideal
+    pleated-sheet geometry: no trained checkpoint is in the tree, so their effect on sample quality is unmeasured."""
+
+    def __init__(self, n_res, alphas_cumprod, antiparallel=None, antiparallel_weight=1.0, parallel=None, parallel_weight=1.0, ladder=None,
+                 ladder_weight=1.0, table=None, separation=(3, 5), tausq=1.0, device='cuda'):
+        import math
+        self.n_res = int(n_res)
+        if self.n_res < 1:
+            raise ValueError('n_res must be at least 1, got %r' % (n_res,))
+        if antiparallel is None and parallel is None and not ladder:
+            raise ValueError('no term enabled: give antiparallel, parallel or ladder')
+        weights = dict(antiparallel_weight=antiparallel_weight, parallel_weight=parallel_weight, ladder_weight=ladder_weight)
+        for name, v in weights.items():
+            if not (math.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, v))
+        bounds = {}
+        for name, v in (('antiparallel', antiparallel), ('parallel', parallel)):
+            if v is None:
+                bounds[name] = None
+                continue
+            try:
+                lo, hi = (float(e) for e in v)
+            except (TypeError, ValueError):
+                raise ValueError('%s must be (min, max), got %r' % (name, v)) from None
+            if not 0.0 <= lo <= hi or math.isinf(lo):
+                raise ValueError('%s needs 0 <= min <= max with min finite, got %r' % (name, v))
+            bounds[name] = (lo, hi)
+        try:
+            sep = tuple(separation)
+        except TypeError:
+            sep = ()
+        if len(sep) != 2 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 3 for v in sep):
+            raise ValueError('separation must be two integers >= 3 (antiparallel, parallel), got %r' % (separation,))
+        if not (math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        if table is None:
+            table = capi.SHEET_TABLE
+        table = tuple(float(v) for v in (table.reshape(-1).tolist() if torch.is_tensor(table) else table))
+        if len(table) != 4 or not all(math.isfinite(v) for v in table):
+            raise ValueError('table must hold 4 finite numbers (mu_A, sigma_A, mu_P, sigma_P), got %r' % (table,))
+        if min(table[1], table[3]) <= 0:
+            raise ValueError('every sigma of the table must be > 0, got %r' % ((table[1], table[3]),))
+        self.rungs = check_ladder(ladder or [], self.n_res)
+        # a term that is off is a weight of 0 to the entry
+        self.antiparallel, self.antiparallel_weight = \
+            ((0.0, math.inf), 0.0) if bounds['antiparallel'] is None else (bounds['antiparallel'], float(antiparallel_weight))
+        self.parallel, self.parallel_weight = \
+            ((0.0, math.inf), 0.0) if bounds['parallel'] is None else (bounds['parallel'], float(parallel_weight))
+        self.ladder_weight = float(ladder_weight) if self.rungs else 0.0
+        self.table, self.separation = table, (int(sep[0]), int(sep[1]))
+        lad = ladder_table(self.rungs, self.n_res, table)
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.L2 = int(lad[1].numel())
+        self.ladder = tuple(t.to(self.device) for t in lad) if self.L2 else (None,) * 4
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, want='report')                 # (the energies do not depend on var)
+        return _decode_report(report, capi.SHEET_REPORT, capi.SHEET_COUNTS)
+
+    def pairs(self, x):
+        """Every residue's partners in every sample of x [B,N,3]: int32 [B, N, 2] (antiparallel, parallel; -1: none), on the
+        potential's device."""
+        return self._launch(self._checked(x), self._one, want='pairs')[0]
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous) for the outputs `want` names, the others passed as NULL: 'logp' gives (logp,
+        grad), 'report' (report [B, 9],), 'pairs' (pairs [B, N, 2],)."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        outs = [None, None, None, None]
+        if want == 'logp':
+            outs[:2] = torch.empty(B, **f32), torch.empty_like(x)
+        elif want == 'report':
+            outs[2] = torch.empty(B, len(capi.SHEET_REPORT), **f32)
+        else:
+            outs[3] = torch.empty(B, self.n_res, 2, dtype=torch.int32, device=x.device)
+        self._call('genie_sheet_potential', self._stream(), B, self.n_res, _ptr(x), *self.table, *self.separation, self.antiparallel[0],
+                   self.antiparallel[1], self.antiparallel_weight, self.parallel[0], self.parallel[1], self.parallel_weight, self.L2,
+                   *(_ptr(t) for t in self.ladder), self.ladder_weight, _ptr(var), *(_ptr(t) for t in outs),
+                   *self._workspace(self.lib.genie_sheet_potential_work_bytes(B, self.n_res)))
+        return tuple(t for t in outs if t is not None)
+
+
 class SumPotential:
     """The sum of twisting functions: `SumPotential(a, b, ...)(x0, step) = a(x0, step) + b(x0, step) + ...`, added in that order.
     `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential); `describe` is the merge of the reports
     of every member that has one (ShapePotential, SecStructPotential), in member order, the first member winning on a key two of them
-    report; `assign` is that of the first member that has one (SecStructPotential).  An attribute no member has is absent, so
-    TwistedSampler's hasattr checks see through the sum."""
+    report; `assign` is that of the first member that has one (SecStructPotential), `pairs` likewise (SheetPotential).  An attribute no
+    member has is absent, so TwistedSampler's hasattr checks see through the sum."""
 
     def __init__(self, *potentials):
         if not potentials:
@@ -898,10 +1095,11 @@ class SumPotential:
                 break
         if any(hasattr(m, 'describe') for m in self.potentials):
             self.describe = self._describe
-        for m in self.potentials:
-            if hasattr(m, 'assign'):
-                self.assign = m.assign
-                break
+        for name in ('assign', 'pairs'):
+            for m in self.potentials:
+                if hasattr(m, name):
+                    setattr(self, name, getattr(m, name))
+                    break
 
     def _describe(self, x):
         out = {}

@@ -5,9 +5,10 @@
  * The reference has no FFI of its own: its seam is the Python
  * call `self.model.model(ts, timesteps, features)['z']` inside the reverse
  * loop.  Each entry point below names the reference code it replaces
- * (paths relative to the reference root); genie_shape_potential, the
- * shape potential of guided sampling, has no counterpart there and says so,
- * and genie_secstruct_potential has no differentiable one.
+ * (paths relative to the reference root); genie_shape_potential and
+ * genie_sheet_potential, the shape and the strand-pairing potential of guided
+ * sampling, have no counterpart there and say so, and
+ * genie_secstruct_potential has no differentiable one.
  *
  * Conventions
  *   - return 0 = ok, < 0 = error (GENIE_E_*); text via genie_last_error().
@@ -309,7 +310,7 @@ size_t genie_shape_potential_work_bytes(int B, int N);
  * the likelihood is left unnormalised.
  * Hard assignment (for reporting, not differentiated): window i is class c when all four |z_cf| <= 1; residue n is H if any window
  * containing it is H, otherwise E if any is E, otherwise C.  assign_out[b,n] is 0 C, 1 H, 2 E.  "Extended" is local geometry only:
- * there is no strand pairing.  report_out[b] holds GENIE_SECSTRUCT_REPORT floats:
+ * there is no strand pairing (genie_sheet_potential, below, scores it).  report_out[b] holds GENIE_SECSTRUCT_REPORT floats:
  *   helix_content (n_H / W), extended_content (n_E / W), n_helix, n_extended (residues of the hard assignment), e_helix, e_extended,
  *   e_target (the weighted E above, before the division by 2 var), n_target_missed (residues with target H or E whose hard
  *   assignment differs; 0 with a NULL target)
@@ -331,6 +332,75 @@ int genie_secstruct_potential(genie_stream_t stream, int B, int N, const float* 
                               const int8_t* target /*[N] device, or NULL*/, float target_weight,
                               const float* var /*[1], device*/, float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
                               float* report_out /*[B,GENIE_SECSTRUCT_REPORT] or NULL*/, int8_t* assign_out /*[B,N] or NULL; 0 C, 1 H, 2 E*/);
+
+/* The sheet potential of twisted-diffusion / SMC sampling with its gradient, a per-particle report and every residue's pairing
+ * partner, without a handle: soft bounds on the antiparallel and the parallel strand-pairing content and an optional ladder of
+ * listed rungs, scored on C-alpha distances alone (csrc/sheet_kernels.hip).  It is what genie_secstruct_potential's "extended" class
+ * leaves out; the reference has no counterpart.  For particle b with coordinates x_n (n = 0..N-1, Angstrom; all N rows are used)
+ * and class c in {A (antiparallel), P (parallel)} a rung is a pair (i, j) of interior residues, 1 <= i < j <= N-2, j - i >= sep_c,
+ * with three distances
+ *   A: d0 = |x_i - x_j|,  d1 = |x_{i-1} - x_{j+1}|,  d2 = |x_{i+1} - x_{j-1}|
+ *   P: d0 = |x_i - x_j|,  d1 = |x_{i-1} - x_{j-1}|,  d2 = |x_{i+1} - x_{j+1}|
+ * (the neighbours of a paired residue are paired with the neighbours of its partner, in the opposite or in the same direction).
+ * Four floats passed by value hold a target and a tolerance per class: mu_A = 5.0, sigma_A = 0.6, mu_P = 4.8, sigma_P = 0.5 A are the
+ * defaults the Python layer passes.  Per rung
+ *   z_f = (d_f - mu_c) / sigma_c,   u_c,ij = 1/3 sum_f z_f^2,   s_c,ij = 1 / (1 + u_c,ij)^2,   n_c = sum_rungs s_c,ij
+ * (squared-rational: the plain 1 / (1 + u) of the secondary-structure potential decays so slowly that the far pairs of a compact
+ * chain add up to more than the signal of a sheet; this one still needs no exp), and with the soft rung count n_c
+ *   E_c   = c_weight * [ max(0, N c_min - n_c)^2 + max(0, n_c - N c_max)^2 ]       c = antiparallel, parallel
+ *   E_lad = ladder_weight * sum_r w_r u_{c_r}(i_r, j_r)                            over the listed rungs r = (i_r, j_r, c_r, w_r)
+ *   logp_out[b] = -(E_A + E_P + E_lad) / (2 var)
+ *   grad_out[b,n] = d logp[b] / d x_n, analytic, with d s / d u = -2 / (1 + u)^3 and d u / d d_f = 2 z_f / (3 sigma_c)
+ * The bounds are in rungs per residue (an interior strand of a large sheet approaches 1); c_max = +inf is no upper bound.  Counts,
+ * not fractions, enter the hinge.  A distance that is exactly 0 in float32 has direction 0: every output is finite for finite
+ * inputs.  A weight of 0 switches its term off (energy and force).  `var` is one float in device memory; the likelihood is left
+ * unnormalised.  N < 6 has no eligible rung: n_c = 0, logp from the hinges alone, a gradient of 0 and every partner -1.
+ * The ladder arrives as a per-residue table of harmonic distance terms the host builds once (device memory), since u is a sum of
+ * three squared distance deviations: E_lad = ladder_weight * sum_terms coef (|x_p - x_q| - mu)^2, coef = w_r / (3 sigma_c^2), the
+ * coefficients of a distance that neighbouring rungs of one class share merged.  The entries of residue n are lad_offset[n] ..
+ * lad_offset[n+1] - 1 (lad_offset[0] = 0, lad_offset[N] = L2), entry k naming the partner in the low bits of lad_partner[k], its mu
+ * and coef.  Every term is listed at both of its residues (L2 = twice their number), partners ascending within a residue, so a
+ * residue's force is a gather in a fixed order; energies are taken from the entries with partner > residue.  lad_partner[k] also
+ * carries GENIE_SHEET_PARALLEL where the term belongs to class P and GENIE_SHEET_RUNG where it is the d0 of a listed rung (those
+ * entries are what n_ladder_missed counts).  L2 = 0: no ladder, the four pointers may be NULL.  The caller validates the table;
+ * offsets and partners are clamped into range all the same.
+ * Hard assignment (for reporting, not differentiated): a rung is formed in class c when all three |z_f| <= 1; a residue is paired
+ * when it is the i or the j of a formed rung.  pairs_out[b,n,0] is the partner of residue n's formed antiparallel rung with the
+ * highest s, pairs_out[b,n,1] the same for parallel; -1: none; of equal s the lowest partner.  report_out[b] holds
+ * GENIE_SHEET_REPORT floats:
+ *   antiparallel_content (n_A / N), parallel_content (n_P / N), n_antiparallel, n_parallel (formed rungs), n_paired (paired
+ *   residues), e_antiparallel, e_parallel, e_ladder (the weighted E above, before the division by 2 var), n_ladder_missed (listed
+ *   rungs that are not formed in their class, whatever their separation; 0 without a ladder)
+ * (counts are stored as floats: exact up to 2^24).  logp_out and grad_out are given together or both NULL; report_out and pairs_out
+ * may be NULL; at least one output is asked for.
+ * Two launches on `stream`: grid (ceil(N / 64), B) work-groups that stage x0[b] in LDS (12 N + 14 336 bytes), walk all partners of
+ * their 64 residues as a gather (a rung's force lands on six residues: each lane recomputes, per partner, the up to six rungs that
+ * hold that distance from nine distances, and no lane writes another lane's residue) and leave three unscaled gradient fields and 8
+ * partial values per tile in `work` (genie_sheet_potential_work_bytes(B, N) = B * (36 N + 32 ceil(N / 64)) bytes, 4-byte aligned);
+ * then the same grid with 64 threads adds the tiles in tile order, forms the hinge coefficients, which depend on the particle-wide
+ * n_c, and writes the gradient, logp and the report.  With both class weights 0 and neither report nor pairs asked for the pair walk
+ * is skipped.  No allocation, no synchronisation, no host read, no atomics: every output is written once in a fixed order, so two
+ * calls on the same inputs are bitwise equal.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 1; x0 or var NULL; no output asked for; logp_out and grad_out not given together; a separation below 3; a sigma that is
+ * <= 0 or not finite (or a mu that is not finite); a negative or non-finite weight; a bound that is negative or NaN, an infinite
+ * minimum, or min > max; L2 < 0, L2 odd, or L2 > 0 with a NULL table; `work` NULL, misaligned or work_bytes too small; an N whose
+ * staging does not fit in LDS (160 KiB: N above 12 458). */
+#define GENIE_SHEET_REPORT 9   /* antiparallel_content, parallel_content, n_antiparallel, n_parallel, n_paired, e_antiparallel,
+                                  e_parallel, e_ladder, n_ladder_missed */
+#define GENIE_SHEET_PARALLEL (1 << 29)   /* lad_partner flag: the term belongs to class P */
+#define GENIE_SHEET_RUNG (1 << 30)       /* lad_partner flag: the term is the d0 of a listed rung */
+int genie_sheet_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/,
+                          float mu_antiparallel, float sigma_antiparallel, float mu_parallel, float sigma_parallel,
+                          int separation_antiparallel, int separation_parallel,
+                          float antiparallel_min, float antiparallel_max, float antiparallel_weight,
+                          float parallel_min, float parallel_max, float parallel_weight,
+                          int L2, const int32_t* lad_offset /*[N+1]*/, const int32_t* lad_partner /*[L2]*/, const float* lad_mu,
+                          const float* lad_coef /*[L2] each*/, float ladder_weight, const float* var /*[1], device*/,
+                          float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                          float* report_out /*[B,GENIE_SHEET_REPORT] or NULL*/, int32_t* pairs_out /*[B,N,2] or NULL; -1: none*/,
+                          void* work, size_t work_bytes);
+size_t genie_sheet_potential_work_bytes(int B, int N);
 
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
