@@ -109,8 +109,12 @@ class GenieEngine:
         """features: the reference's batched feature dict (torch tensors)."""
         f = {k: self._dev(features[k], dt) for k, dt in _FEATURE_DTYPES.items()}
         B, N = f['residue_mask'].shape
-        if int(f['residue_index'].max()) >= self.n_pos or int(f['chain_index'].max()) >= self.n_chain:
+        ri, ci = f['residue_index'], f['chain_index']
+        ri_max, ri_min, ci_max, ci_min = torch.stack([ri.max(), ri.min(), ci.max(), ci.min()]).tolist()      # one read-back
+        if ri_max >= self.n_pos or ci_max >= self.n_chain:
             raise capi.GenieError('residue_index / chain_index exceed the uploaded encoding tables')
+        if ri_min < 0 or ci_min < 0:          # k_single_input would clamp them to row 0 without a word
+            raise capi.GenieError('residue_index / chain_index must not be negative')
         gf = capi.GenieFeatures(**{k: f[k].data_ptr() for k in _FEATURE_DTYPES})
         with torch.cuda.device(self.device):
             rc = self.lib.genie_prepare_features(self._h, self._stream(), B, N, C.byref(gf))
