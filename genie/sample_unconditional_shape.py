@@ -1,12 +1,13 @@
-"""python genie/sample_unconditional_shape.py --name ... --rog_max ... (the unconditional flags plus the shape, secondary-structure
-and sheet terms)."""
+"""python genie/sample_unconditional_shape.py --name ... --rog_max ... (the unconditional flags plus the shape, secondary-structure,
+sheet and symmetry terms)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from genie2_amd.sample_unconditional_shape import (ShapeRunner, add_secstruct_arguments, add_sheet_arguments,  # noqa: E402,F401
-                                                   build_parser, main, secstruct_constants, secstruct_potential, sheet_constants,
-                                                   sheet_potential)
+                                                   add_symmetry_arguments, build_parser, main, secstruct_constants,
+                                                   secstruct_potential, sheet_constants, sheet_potential, symmetry_constants,
+                                                   symmetry_potential)
 
 if __name__ == '__main__':
     main(build_parser().parse_args())

@@ -117,6 +117,9 @@ SYMBOLS = {
     'genie_sheet_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_float] * 6 +
                               [C.c_int] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 6 + [C.c_size_t]),
     'genie_sheet_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'genie_symmetry_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float] +
+                                 [C.c_void_p] * 5 + [C.c_size_t]),
+    'genie_symmetry_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -134,6 +137,9 @@ SHEET_COUNTS = ('n_antiparallel', 'n_parallel', 'n_paired', 'n_ladder_missed')
 # alternate around 4.5 / 5.5 A)
 SHEET_TABLE = (5.0, 0.6, 4.8, 0.5)
 SHEET_PARALLEL, SHEET_RUNG = 1 << 29, 1 << 30       # GENIE_SHEET_PARALLEL, GENIE_SHEET_RUNG: flags of a ladder table's partner words
+
+SYMMETRY_REPORT = ('e_symmetry', 'symmetry_rmsd', 'rmsd_0', 'angle_0', 'rise_0', 'rmsd_1', 'angle_1', 'rise_1')      # GENIE_SYMMETRY_REPORT slots
+SYMMETRY_MAX_GENERATORS = 2     # GENIE_SYMMETRY_MAX_GENERATORS
 
 _lib = None
 

@@ -65,7 +65,7 @@ class GenieEngine:
         assert blob.numel() == self.lib.genie_weight_count(C.byref(cd))
         capi.check(self._h, self.lib.genie_load_weights(self._h, _ptr(blob), blob.numel()), 'genie_load_weights')
         self.n_pos = int(n_pos or max(self.dims['max_n_res'], 1))
-        self.n_chain = int(n_chain or max(self.dims['max_n_chain'], 8))
+        self.n_chain = int(n_chain or pack.chain_table_rows(self.dims))
         self.schedule = pack.schedule_tensors(self.dims['n_timestep'])
         pos = pack.sinusoidal_table(self.n_pos, self.dims['max_n_res'], self.dims['c_pos_emb'])
         chn = pack.sinusoidal_table(self.n_chain, self.dims['max_n_chain'], self.dims['c_chain_emb'])

@@ -29,6 +29,11 @@ def engine_dims(dims):
     return out
 
 
+def chain_table_rows(dims):
+    """The rows of the chain-embedding table GenieEngine uploads by default: the chains one structure may hold."""
+    return max(int(dims['max_n_chain']), 8)
+
+
 def _linear(out, prefix, o, i, bias=True):
     out.append((prefix + '.weight', (o, i)))
     if bias:

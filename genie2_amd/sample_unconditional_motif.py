@@ -35,14 +35,18 @@ motif, shape, secondary structure, `--write_secstruct` writes outdir/secstruct/{
 other than the blueprint's are skipped.
 
 `--antiparallel_min` / `--antiparallel_max`, `--parallel_min` / `--parallel_max` and `--ladder_file` (with their weights and
-`--sheet_tausq`: the flags of add_sheet_arguments in the same module) add strand-pairing guidance, summed last; `--write_sheet` writes
-outdir/sheet/{length}_{index}.txt as that CLI does, and lengths that cannot hold the ladder are skipped."""
+`--sheet_tausq`: the flags of add_sheet_arguments in the same module) add strand-pairing guidance, summed after them; `--write_sheet`
+writes outdir/sheet/{length}_{index}.txt as that CLI does, and lengths that cannot hold the ladder are skipped.
+
+`--symmetry C<n>|D<n>|R<n>` (with `--unit_length`, `--unit_linker`, `--unit_offset`, `--symmetry_weight`, `--symmetry_tausq`,
+`--unit_chains` and `--write_symmetry`: the flags of add_symmetry_arguments in the same module) adds symmetry guidance, summed last;
+`--write_symmetry` writes outdir/symmetry/{length}_{index}.txt as that CLI does, and lengths the layout does not fit are skipped."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
 from .sample_unconditional_shape import (GuidedRunner, add_guidance_arguments, add_secstruct_arguments, add_shape_arguments,
-                                         add_sheet_arguments)
+                                         add_sheet_arguments, add_symmetry_arguments)
 
 
 def load_motif_segments(filepath):
@@ -138,6 +142,7 @@ def build_parser():
     add_shape_arguments(p)
     add_secstruct_arguments(p)
     add_sheet_arguments(p)
+    add_symmetry_arguments(p)
     return p
 
 

@@ -2,7 +2,7 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure or sheet term (below), is needed.
+least one of the three, or a secondary-structure, sheet or symmetry term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -26,9 +26,18 @@ class A pairs i + k with j - k, class P pairs i + k with j + k, k = 0..len-1; `#
 ladder is skipped.  `--write_sheet` adds outdir/sheet/{length}_{index}.txt: one `i j A|P` line per formed rung of the written
 structure (each rung once, i < j), then one `key value` line per field of SheetPotential.describe.
 
+`--symmetry C<n>|D<n>|R<n>` guides the chain to repeat itself: n units around an n-fold axis (a cyclic oligomer, a closed toroid), 2n
+units in two rings related by a two-fold, or n units along one screw (an open repeat): a SymmetryPotential
+(csrc/symmetry_kernels.hip), summed last and enough on its own.  `--unit_length` (default: the length divided evenly), `--unit_linker`
+and `--unit_offset` lay the units out, `--symmetry_weight` and `--symmetry_tausq` scale the term; a length the layout does not fit is
+skipped.  `--unit_chains` samples and writes the units as chains A, B, ... (no linker, no offset, units that fill the length).
+`--write_symmetry` adds outdir/symmetry/{length}_{index}.txt: the line `symmetry C3 units 3 unit_length 20 linker 0 offset 0`, then
+one `key value` line per field of SymmetryPotential.describe.  Units can satisfy the term by lying on top of each other, which
+`--clash_distance` prevents; `--rog_max` over the assembly keeps separate chains together.
+
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
-add_shape_arguments, add_secstruct_arguments and add_sheet_arguments too and then guides with the sum of the potentials asked for."""
+add_shape_arguments, add_secstruct_arguments, add_sheet_arguments and add_symmetry_arguments too and then guides with the sum of the potentials asked for."""
 import os
 
 from tqdm import tqdm
@@ -40,6 +49,7 @@ COUNTS = ('n_clash', 'n_violated')
 SECSTRUCT_KEYS = ('helix_weight', 'extended_weight', 'ss_target_weight', 'ss_tausq')
 SECSTRUCT_COUNTS = ('n_helix', 'n_extended', 'n_target_missed')
 SHEET_KEYS = ('antiparallel_weight', 'parallel_weight', 'ladder_weight', 'sheet_tausq')
+SYMMETRY_KEYS = ('symmetry', 'unit_length', 'unit_linker', 'unit_offset', 'symmetry_weight', 'symmetry_tausq')
 
 
 def add_shape_arguments(parser):
@@ -250,6 +260,91 @@ def write_sheet_report(pairs, report, directory, length, offset):
     write_report(report, SHEET_COUNTS, directory, length, offset, ['\n'.join(formed_rungs(row)) for row in pairs])
 
 
+def add_symmetry_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    parser.add_argument('--symmetry', type=str, default=None,
+                        help='Guide the chain to repeat itself: C<n> (n units around an n-fold axis: a cyclic oligomer or a closed toroid), '
+                             'D<n> (2n units, two rings related by a two-fold), R<n> (n units along one screw: an open repeat); default: '
+                             'no such term' + tail)
+    parser.add_argument('--unit_length', type=int, default=None,
+                        help='Residues per unit; default: what is left of the length, divided evenly' + tail)
+    parser.add_argument('--unit_linker', type=int, default=0, help='Free residues between two units' + tail)
+    parser.add_argument('--unit_offset', type=int, default=0, help='Free residues before the first unit' + tail)
+    parser.add_argument('--symmetry_weight', type=float, default=1.0, help='Weight of the symmetry term' + tail)
+    parser.add_argument('--symmetry_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the symmetry term, Angstrom^2' + tail)
+    parser.add_argument('--unit_chains', action='store_true',
+                        help='Sample and write the units as separate chains A, B, ... (needs --unit_linker 0, --unit_offset 0 and units '
+                             'that fill the length)' + tail)
+    parser.add_argument('--write_symmetry', action='store_true',
+                        help='Write outdir/symmetry/{length}_{index}.txt: the layout, then the symmetry energy, RMSDs, rotation angles and '
+                             'rises of every written structure' + tail)
+
+
+def symmetry_constants(params):
+    """The symmetry keys of a runner's constants: the flags of add_symmetry_arguments.  A symbol that does not parse, and
+    --unit_chains without --symmetry or with a linker or an offset, end the run here."""
+    from .smc import parse_symmetry
+    defaults = dict(symmetry=None, unit_length=None, unit_linker=0, unit_offset=0, symmetry_weight=1.0, symmetry_tausq=1.0)
+    c = {k: params.get(k, defaults[k]) for k in SYMMETRY_KEYS}
+    c['unit_chains'] = bool(params.get('unit_chains', False))
+    c['write_symmetry'] = bool(params.get('write_symmetry', False))
+    if c['symmetry'] is not None:
+        try:
+            parse_symmetry(c['symmetry'])
+        except ValueError as e:
+            raise SystemExit('--symmetry: %s' % e) from None
+    if c['unit_chains'] and (c['symmetry'] is None or c['unit_linker'] or c['unit_offset']):
+        raise SystemExit('--unit_chains needs --symmetry with --unit_linker 0 and --unit_offset 0: a chain is a unit, nothing else')
+    return c
+
+
+def has_symmetry_terms(constants):
+    return constants.get('symmetry') is not None
+
+
+def symmetric_lengths(tasks, constants):
+    """The tasks whose length the symmetric layout fits (symmetry_layout's rules; with --unit_chains the units fill the length); the
+    others are skipped with one printed line."""
+    if not has_symmetry_terms(constants):
+        return tasks
+    from .smc import symmetry_layout
+
+    def fits(length):
+        try:
+            units, m = symmetry_layout(constants['symmetry'], length, constants['unit_length'], constants['unit_linker'], constants['unit_offset'])
+        except ValueError:
+            return False
+        return not constants['unit_chains'] or units * m == length
+
+    other = [t['length'] for t in tasks if not fits(t['length'])]
+    if other:
+        print('skipping lengths the {} layout does not fit: {}'.format(constants['symmetry'], ', '.join(map(str, other))))
+    return [t for t in tasks if fits(t['length'])]
+
+
+def symmetry_potential(constants, length, abar, device):
+    """The SymmetryPotential the constants ask for at this length, or None when they ask for no term.  (Lengths the layout does not
+    fit never get here: symmetric_lengths drops them when the tasks are made.)"""
+    if not has_symmetry_terms(constants):
+        return None
+    from .smc import SymmetryPotential
+    return SymmetryPotential(length, abar, symmetry=constants['symmetry'], unit_length=constants['unit_length'],
+                             linker=constants['unit_linker'], offset=constants['unit_offset'], weight=constants['symmetry_weight'],
+                             tausq=constants['symmetry_tausq'], device=device)
+
+
+def symmetry_header(potential):
+    """The first line of a symmetry report: `symmetry C3 units 3 unit_length 20 linker 0 offset 0`."""
+    return 'symmetry {} units {} unit_length {} linker {} offset {}'.format(potential.symmetry, potential.units, potential.unit_length,
+                                                                            potential.linker, potential.offset)
+
+
+def write_symmetry_report(report, header, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: the layout line `header`, then a `key value` line per field of
+    `report` (the symmetry fields of last_shape), %.3f."""
+    write_report(report, (), directory, length, offset, [header] * len(next(iter(report.values()))))
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -294,13 +389,13 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape, secondary-structure and sheet potentials the constants ask for, in
-    that order; `after_batch` writes a subclass's own reports."""
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet and symmetry potentials the constants ask
+    for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
 
     def guided_lengths(self, tasks, params):
-        """The tasks whose length the restraints, the blueprint and the ladder allow."""
+        """The tasks whose length the restraints, the blueprint, the ladder and the symmetric layout allow."""
         tasks = target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
-        return ladder_lengths(tasks, sheet_constants(params)['ladder'])
+        return symmetric_lengths(ladder_lengths(tasks, sheet_constants(params)['ladder']), symmetry_constants(params))
 
     def create_tasks(self, params):
         return self.guided_lengths(super().create_tasks(params), params)
@@ -312,6 +407,7 @@ class GuidedRunner(UnconditionalRunner):
         c.update(shape_constants(params))
         c.update(secstruct_constants(params))
         c.update(sheet_constants(params))
+        c.update(symmetry_constants(params))
         return c
 
     def batch_potentials(self, constants, length, abar, device):
@@ -333,14 +429,17 @@ class GuidedRunner(UnconditionalRunner):
             shape = shape_potential(constants, length, abar, device)
             secstruct = secstruct_potential(constants, length, abar, device)
             sheet = sheet_potential(constants, length, abar, device)
+            symmetry = symmetry_potential(constants, length, abar, device)
+            chains = {'chain_lengths': symmetry.chain_lengths()} if constants['unit_chains'] else {}
             for batch, offset in self.batches(constants, outdir, length):
                 sampler.sample({
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
-                    'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet),
+                    'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet,
+                                                        symmetry),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
-                    'num_steps': constants.get('num_steps'), **systems, **self.partial_params(constants)})
+                    'num_steps': constants.get('num_steps'), **systems, **chains, **self.partial_params(constants)})
                 if constants.get('write_start_rmsd'):
                     write_start_rmsd(sampler.last_start_rmsd, os.path.join(outdir, 'start_rmsd'),
                                      ['{}_{}'.format(length, offset + i) for i in range(batch)])
@@ -353,15 +452,18 @@ class GuidedRunner(UnconditionalRunner):
                 if constants['write_sheet'] and sheet is not None:
                     write_sheet_report(sampler.last_pairs, report_fields(sampler.last_shape, capi.SHEET_REPORT),
                                        os.path.join(outdir, 'sheet'), length, offset)
+                if constants['write_symmetry'] and symmetry is not None:
+                    write_symmetry_report(report_fields(sampler.last_shape, capi.SYMMETRY_REPORT), symmetry_header(symmetry),
+                                          os.path.join(outdir, 'symmetry'), length, offset)
 
 
 class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
-        if not has_shape_terms(c) and not has_secstruct_terms(c) and not has_sheet_terms(c):
+        if not has_shape_terms(c) and not has_secstruct_terms(c) and not has_sheet_terms(c) and not has_symmetry_terms(c):
             raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
-                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target) or a sheet term '
-                             '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file)')
+                             'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target), a sheet term '
+                             '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file) or --symmetry')
         return c
 
 
@@ -372,6 +474,7 @@ def build_parser():
     add_shape_arguments(p)
     add_secstruct_arguments(p)
     add_sheet_arguments(p)
+    add_symmetry_arguments(p)
     return p
 
 

@@ -248,7 +248,21 @@ class UnconditionalSampler(BaseSampler):
         os.makedirs(os.path.join(params['outdir'], 'pdbs'), exist_ok=True)
 
     def create_np_features(self, params):
-        return F.create_empty_np_features([params['length']])
+        """One chain of params['length'] residues, or (not in the reference's sampler; its features and the denoiser have them) the
+        chains of params['chain_lengths']: positive integers that sum to the length, at most as many as the engine's chain table has
+        rows.  SymmetryPotential.chain_lengths() gives the units of a symmetric design."""
+        chains = params.get('chain_lengths')
+        if chains is None:
+            return F.create_empty_np_features([params['length']])
+        chains = list(chains)
+        if not chains or any(isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1 for n in chains):
+            raise ValueError('chain_lengths must be positive integers, got %r' % (chains,))
+        if sum(chains) != params['length']:
+            raise ValueError('chain_lengths %r sum to %d, the length is %d' % (chains, sum(chains), params['length']))
+        rows = pack.chain_table_rows(self.model.model.dims)
+        if len(chains) > rows:
+            raise ValueError('%d chains, the engine\'s chain table holds %d' % (len(chains), rows))
+        return F.create_empty_np_features(chains)
 
     def on_sample_end(self, params, list_np_features):
         for i, np_features in enumerate(list_np_features):

@@ -7,7 +7,8 @@ MotifPotential (appended below) as its one-pass HIP form (csrc/smc_kernels.hip).
 gyration, clashes, distance restraints; not in the reference) is the second built-in potential, SecStructPotential
 (csrc/secstruct_kernels.hip: helix / extended content and a blueprint; the reference's sampler/secstruct.py runs P-SEA on the host and
 is not differentiable) the third, SheetPotential (csrc/sheet_kernels.hip: antiparallel / parallel strand pairing and a ladder of listed
-rungs; not in the reference) the fourth, and SumPotential adds potentials.
+rungs; not in the reference) the fourth, SymmetryPotential (csrc/symmetry_kernels.hip: cyclic, dihedral and repeat symmetry by
+superposing units under the group's generators; not in the reference) the fifth, and SumPotential adds potentials.
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -128,14 +129,14 @@ class TwistedSampler(UnconditionalSampler):
     or, instead, 'motif_target' (list of [n_i, 3] segments: the placements are enumerated with generate_motif_index_mask and the
     potential is motif_twisting_function over all of them, unconditional_smc.py:303-345); optional 'tausq' with it;
     optional 'noise' [T,B,N,3] (initial draw + one per step, as BaseSampler), 'resample_u' (list of uniforms, tests),
-    'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50).
+    'guidance_alpha' (default 0.012), 'ess_threshold' (default 0.5), 'last_unguided_steps' (default 50), 'chain_lengths' (the
+    UnconditionalSampler's: the structure as several chains, e.g. SymmetryPotential.chain_lengths()).
     After _sample, `last_fit` holds what the twisting function's `locate` says of the final coordinates (MotifPotential.locate: 'best',
     'rmsd', 'starts', 'ends' as CPU tensors, one row per returned sample; with motif groups also 'group_rmsd' and the 'groups' labels),
     or None when it has no `locate`; `last_shape` what its `describe` says of them (ShapePotential.describe: 'rog', 'min_distance',
     'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation' as CPU tensors, one row per returned sample; with a
-    SecStructPotential its eight fields, with a SheetPotential its nine, and with a SumPotential every member's), or None when it
-    has no `describe`; `last_secstruct`
-    what its `assign` says of them (SecStructPotential.assign: int8 [rows, N] on the CPU, 0 C, 1 H, 2 E), or None when it has no
+    SecStructPotential its eight fields, with a SheetPotential its nine, with a SymmetryPotential its eight, and with a SumPotential
+    every member's), or None when it has no `describe`; `last_secstruct` what its `assign` says of them (SecStructPotential.assign: int8 [rows, N] on the CPU, 0 C, 1 H, 2 E), or None when it has no
     `assign`; `last_pairs` what its `pairs` says of them (SheetPotential.pairs: int32 [rows, N, 2] on the CPU, every residue's
     antiparallel and parallel partner, -1 for none), or None when it has no `pairs`.
     Optional 'num_steps' = K (not in the reference) visits the K timesteps of pack.respaced_steps with the ancestral kernel between
@@ -1075,6 +1076,187 @@ class SheetPotential(_HipPotential):
                    self.antiparallel[1], self.antiparallel_weight, self.parallel[0], self.parallel[1], self.parallel_weight, self.L2,
                    *(_ptr(t) for t in self.ladder), self.ladder_weight, _ptr(var), *(_ptr(t) for t in outs),
                    *self._workspace(self.lib.genie_sheet_potential_work_bytes(B, self.n_res)))
+        return tuple(t for t in outs if t is not None)
+
+
+def parse_symmetry(symmetry):
+    """A symmetry symbol -> (kind, n, units): 'C3' is ('C', 3, 3), 'D2' ('D', 2, 4), 'R4' ('R', 4, 4); n >= 2.  Anything else is a
+    ValueError."""
+    text = symmetry.strip().upper() if isinstance(symmetry, str) else ''
+    if len(text) < 2 or text[0] not in 'CDR' or not text[1:].isdigit() or int(text[1:]) < 2:
+        raise ValueError("symmetry must be C<n>, D<n> or R<n> with n >= 2 (a cyclic or dihedral group, n repeats), got %r" % (symmetry,))
+    n = int(text[1:])
+    return text[0], n, 2 * n if text[0] == 'D' else n
+
+
+def symmetry_layout(symmetry, n_res, unit_length=None, linker=0, offset=0):
+    """The units of a symmetric chain of n_res residues, validated on the host: (units U, unit length m).  Unit k starts at
+    offset + k (m + linker) and offset + U m + (U - 1) linker <= n_res; `unit_length=None` divides what is left of n_res evenly among
+    the units, or is a ValueError when that leaves a remainder.  Every generator of the symbol needs at least 3 pairs."""
+    kind, n, units = parse_symmetry(symmetry)
+    for name, v in (('n_res', n_res), ('linker', linker), ('offset', offset)) + ((('unit_length', unit_length),) if unit_length is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError('%s must be an integer, got %r' % (name, v))
+    if n_res < 1 or linker < 0 or offset < 0:
+        raise ValueError('needs n_res >= 1, linker >= 0 and offset >= 0, got %d, %d and %d' % (n_res, linker, offset))
+    if unit_length is None:
+        left = n_res - offset - (units - 1) * linker
+        if left < units or left % units:
+            raise ValueError('%d residues with offset %d and linker %d do not divide into %d equal units: give unit_length'
+                             % (n_res, offset, linker, units))
+        unit_length = left // units
+    if unit_length < 1:
+        raise ValueError('unit_length must be at least 1, got %d' % unit_length)
+    if offset + units * unit_length + (units - 1) * linker > n_res:
+        raise ValueError('%s with %d units of %d residues, linker %d and offset %d needs %d residues, the chain has %d'
+                         % (symmetry, units, unit_length, linker, offset, offset + units * unit_length + (units - 1) * linker, n_res))
+    pairs = (n - 1) * unit_length if kind == 'R' else units * unit_length
+    if pairs < 3:
+        raise ValueError('%s with units of %d residues has a generator of %d pairs: a superposition needs 3' % (symmetry, unit_length, pairs))
+    return units, int(unit_length)
+
+
+def symmetry_generators(symmetry, unit_length, n_res, linker=0, offset=0):
+    """The generators of a symmetric layout (include/genie_hip.h states them) as [(src, dst), ...] lists of residue indices, one pair
+    of lists per generator: one for C<n> (unit k onto k + 1 mod n) and R<n> (unit k onto k + 1, k = 0..n-2), two for D<n> (the n-fold,
+    which turns the second ring the other way, and the two-fold that swaps the rings).  The layout is validated by symmetry_layout."""
+    kind, n, _ = parse_symmetry(symmetry)
+    units, m = symmetry_layout(symmetry, n_res, unit_length, linker, offset)
+    res = lambda k, a: offset + k * (m + linker) + a      # noqa: E731
+    if kind == 'R':
+        maps = [[(k, k + 1) for k in range(n - 1)]]
+    elif kind == 'C':
+        maps = [[(k, (k + 1) % n) for k in range(n)]]
+    else:
+        maps = [[(k, (k + 1) % n) for k in range(n)] + [(n + k, n + (k - 1) % n) for k in range(n)],
+                [(k, n + k) for k in range(n)] + [(n + k, k) for k in range(n)]]
+    return [([res(k, a) for k, _ in mp for a in range(m)], [res(j, a) for _, j in mp for a in range(m)]) for mp in maps]
+
+
+def check_generators(generators, n_res):
+    """The generators of SymmetryPotential, validated on the host: 1..capi.SYMMETRY_MAX_GENERATORS of them, each (src, dst) with two
+    lists of L >= 3 integers in 0..n_res-1, src_i != dst_i, no residue a source twice and none a destination twice.  Returns them as
+    [(src, dst), ...] lists of ints."""
+    try:
+        generators = [tuple(g) for g in generators]
+    except TypeError:
+        raise ValueError('generators must be a list of (src, dst) pairs of index lists, got %r' % (generators,)) from None
+    if not 1 <= len(generators) <= capi.SYMMETRY_MAX_GENERATORS:
+        raise ValueError('needs 1..%d generators, got %d' % (capi.SYMMETRY_MAX_GENERATORS, len(generators)))
+    out = []
+    for k, g in enumerate(generators):
+        if len(g) != 2:
+            raise ValueError('generator %d: expected (src, dst), got %d entries' % (k, len(g)))
+        src, dst = (v.tolist() if torch.is_tensor(v) else list(v) for v in g)
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in src + dst):
+            raise ValueError('generator %d: residues must be integers' % k)
+        if len(src) != len(dst) or len(src) < 3:
+            raise ValueError('generator %d: needs as many sources as destinations and at least 3 pairs, got %d and %d' % (k, len(src), len(dst)))
+        if not all(0 <= v < n_res for v in src + dst):
+            raise ValueError('generator %d: residues must lie in 0..%d' % (k, n_res - 1))
+        if any(a == b for a, b in zip(src, dst)):
+            raise ValueError('generator %d: a residue is mapped to itself' % k)
+        if len(set(src)) != len(src) or len(set(dst)) != len(dst):
+            raise ValueError('generator %d: a residue is a source twice or a destination twice' % k)
+        out.append(([int(v) for v in src], [int(v) for v in dst]))
+    return out
+
+
+def partner_table(generators, n_res):
+    """The per-residue table genie_symmetry_potential takes, a CPU tensor int32 [G, 2, n_res]: [g][0][i] the residue i maps to as a
+    source of generator g, [g][1][i] the residue that maps to i, -1 for none."""
+    table = torch.full((len(generators), 2, n_res), -1, dtype=torch.int32)
+    for g, (src, dst) in enumerate(generators):
+        table[g, 0, src] = torch.tensor(dst, dtype=torch.int32)
+        table[g, 1, dst] = torch.tensor(src, dtype=torch.int32)
+    return table
+
+
+class SymmetryPotential(_HipPotential):
+    """Symmetry guidance as one HIP pass (genie_symmetry_potential, csrc/symmetry_kernels.hip; include/genie_hip.h states the
+    mathematics): `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside
+    the other built-in potentials (SumPotential adds them).  The chain holds U units of `unit_length` residues, unit k starting at
+    offset + k (unit_length + linker); `symmetry` names how they repeat:
+      'C<n>'  n units related by an n-fold axis: a cyclic oligomer, or a closed single-chain toroid;
+      'D<n>'  2 n units, two rings of n related by a two-fold: a dihedral oligomer;
+      'R<n>'  n units that follow one another by one screw motion: an open repeat protein.
+    Every generator of the symbol maps units onto units; its energy is the squared deviation left after the best proper rotation and
+    translation superposes the sources on their destinations.  log p = -weight sum_g w_g E_g / (2 var), var =
+    xstart_variance(alphas_cumprod[step], tausq) computed on the device, so nothing on the per-step path reads device memory from the
+    host; the forward keeps the gradient the kernel computes and the backward scales it.  The likelihood is unnormalised.  Residues in
+    no unit (before `offset`, in a linker, after the last unit) are free: their gradient is exactly 0.
+    `unit_length=None` divides what is left of n_res evenly (a ValueError when it does not divide).  `generators=[(src, dst), ...]`
+    takes explicit index lists instead of a symbol (check_generators' rules); `generator_weights` the w_g (1 each by default).
+
+    Everything is validated on the host before the device is looked at.  `describe(x)` reports every sample of x with the names of
+    capi.SYMMETRY_REPORT: 'e_symmetry' (the weighted energy, before the division by 2 var), 'symmetry_rmsd' (over all pairs of all
+    generators), and per generator slot 'rmsd_g', 'angle_g' (degrees, 0..180; 360 / n for a closed C<n>, the twist of a repeat) and
+    'rise_g' (Angstrom along the axis; 0 for a closed ring, the rise of a repeat), zeros for an unused slot: [B] tensors on the
+    potential's device.  `chain_lengths()` is [unit_length] * U, what UnconditionalSampler takes as params['chain_lengths'] to emit
+    the units as separate chains; it needs a symbol with linker 0, offset 0 and U unit_length = n_res.
+
+    The defaults (tausq = 1 A^2, weights 1) are design choices: no trained checkpoint is in the tree, so their effect on sample quality
+    is unmeasured.  Units can satisfy the term by lying on top of each other, which a ShapePotential's clash_distance prevents; its
+    rog_max over the assembly keeps separate chains together."""
+
+    def __init__(self, n_res, alphas_cumprod, symmetry=None, unit_length=None, linker=0, offset=0, generators=None, weight=1.0,
+                 generator_weights=None, tausq=1.0, device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or n_res < 1:
+            raise ValueError('n_res must be an integer >= 1, got %r' % (n_res,))
+        if (symmetry is None) == (generators is None):
+            raise ValueError('give either symmetry (C<n>, D<n>, R<n>) or generators')
+        self.symmetry = self.units = self.unit_length = None
+        self.linker, self.offset = linker, offset
+        if symmetry is not None:
+            self.units, self.unit_length = symmetry_layout(symmetry, n_res, unit_length, linker, offset)
+            self.symmetry = symmetry.strip().upper()
+            generators = symmetry_generators(symmetry, self.unit_length, n_res, linker, offset)
+        elif unit_length is not None or linker != 0 or offset != 0:
+            raise ValueError('unit_length, linker and offset describe the layout of a symmetry symbol, not of explicit generators')
+        self.generators = check_generators(generators, int(n_res))
+        G = len(self.generators)
+        if not (math.isfinite(float(weight)) and float(weight) >= 0):
+            raise ValueError('weight must be finite and >= 0, got %r' % (weight,))
+        try:
+            gw = [1.0] * G if generator_weights is None else [float(v) for v in generator_weights]
+        except (TypeError, ValueError):
+            raise ValueError('generator_weights must hold %d numbers, got %r' % (G, generator_weights)) from None
+        if len(gw) != G or not all(math.isfinite(v) and v >= 0 for v in gw):
+            raise ValueError('generator_weights must hold %d finite numbers >= 0, got %r' % (G, generator_weights))
+        if not (math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        self.weight, self.generator_weights = float(weight), tuple(gw)
+        table = partner_table(self.generators, int(n_res))
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.G = G
+        self.partner = table.to(self.device).contiguous()
+
+    def chain_lengths(self):
+        """[unit_length] * U: the units as the chains of params['chain_lengths'].  A layout with a linker, an offset or residues after
+        the last unit has residues in no chain, and explicit generators have no units: a ValueError."""
+        if self.symmetry is None:
+            raise ValueError('explicit generators have no units to emit as chains')
+        if self.linker != 0 or self.offset != 0 or self.units * self.unit_length != self.n_res:
+            raise ValueError('the units are chains only with linker 0, offset 0 and units * unit_length = n_res: %d units of %d, linker %d, '
+                             'offset %d in %d residues' % (self.units, self.unit_length, self.linker, self.offset, self.n_res))
+        return [self.unit_length] * self.units
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, report=True)                   # (the energies do not depend on var)
+        return _decode_report(report, capi.SYMMETRY_REPORT, ())
+
+    def _launch(self, x, var, report=False):
+        """One call of the C entry on x (f32, contiguous): (report [B, 8],) when `report`, else (logp, grad)."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        if report:
+            outs = [None, None, torch.empty(B, len(capi.SYMMETRY_REPORT), **f32)]
+        else:
+            outs = [torch.empty(B, **f32), torch.empty_like(x), None]
+        w = [self.weight * v for v in self.generator_weights] + [0.0]
+        self._call('genie_symmetry_potential', self._stream(), B, self.n_res, _ptr(x), self.G, _ptr(self.partner), w[0], w[1], _ptr(var),
+                   *(_ptr(t) for t in outs), *self._workspace(self.lib.genie_symmetry_potential_work_bytes(B, self.n_res)))
         return tuple(t for t in outs if t is not None)
 
 

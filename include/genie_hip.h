@@ -5,9 +5,10 @@
  * The reference has no FFI of its own: its seam is the Python
  * call `self.model.model(ts, timesteps, features)['z']` inside the reverse
  * loop.  Each entry point below names the reference code it replaces
- * (paths relative to the reference root); genie_shape_potential and
- * genie_sheet_potential, the shape and the strand-pairing potential of guided
- * sampling, have no counterpart there and say so, and
+ * (paths relative to the reference root); genie_shape_potential,
+ * genie_sheet_potential and genie_symmetry_potential, the shape, the
+ * strand-pairing and the symmetry potential of guided sampling, have no
+ * counterpart there and say so, and
  * genie_secstruct_potential has no differentiable one.
  *
  * Conventions
@@ -401,6 +402,60 @@ int genie_sheet_potential(genie_stream_t stream, int B, int N, const float* x0 /
                           float* report_out /*[B,GENIE_SHEET_REPORT] or NULL*/, int32_t* pairs_out /*[B,N,2] or NULL; -1: none*/,
                           void* work, size_t work_bytes);
 size_t genie_sheet_potential_work_bytes(int B, int N);
+
+/* The symmetry potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle: how far a
+ * chain is from repeating itself under one or two generators (csrc/symmetry_kernels.hip).  It is what the other potentials, which all
+ * act inside one asymmetric chain, cannot ask for: a cyclic or dihedral oligomer, a closed toroid of identical units, an open repeat
+ * whose units follow one another by one screw motion.  The reference has no counterpart.
+ * Layout (what the Python layer builds; the entry itself only sees generators): U units of m residues, unit k starting at
+ * offset + k (m + linker), residue (k, a) = start_k + a, offset + U m + (U - 1) linker <= N; residues in no unit are free, and the
+ * gradient there is exactly 0.  A generator is a list of L >= 3 pairs (src_i, dst_i) of distinct residues, no residue a source twice
+ * and none a destination twice within one generator; at most GENIE_SYMMETRY_MAX_GENERATORS of them:
+ *   C<n>, U = n:   g0: (k, a) -> ((k + 1) mod n, a), L = n m
+ *   D<n>, U = 2n:  units 0..n-1 one ring, n..2n-1 the other; g0 (the n-fold): (k, a) -> ((k + 1) mod n, a) for k < n and
+ *                  (n + k, a) -> (n + (k - 1) mod n, a); g1 (the two-fold): (k, a) <-> (n + k, a) in both directions; L = 2 n m each
+ *                  (as permutations g1 g0 g1 = g0^-1 and g0^n = id)
+ *   R<n>, U = n:   g0: (k, a) -> (k + 1, a), k = 0..n-2, L = (n - 1) m: one rigid motion, a screw, carries units 0..n-2 onto 1..n-1
+ * For particle b with coordinates x (Angstrom) and generator g
+ *   c_s = mean_i x[src_i],  c_d = mean_i x[dst_i],  p_i = x[src_i] - c_s,  q_i = x[dst_i] - c_d
+ *   R_g = argmin over proper rotations of sum_i |q_i - R p_i|^2: Horn's quaternion of the correlation sum_i p_i q_i^T (csrc/horn.h, as
+ *         the rigid motif alignment finds it; a proper rotation, so a mirror image does not fit)
+ *   E_g = sum_i |q_i - R_g p_i|^2, summed from the residuals, never as sum |q|^2 + sum |p|^2 - 2 lambda_max: near symmetry that
+ *         difference of large numbers has no digits left
+ *   logp_out[b] = -(weight0 E_0 + weight1 E_1) / (2 var)
+ *   grad_out[b] = d logp[b] / d x, analytic, with R_g held at its optimum (to first order E does not move with R, and the residuals
+ *         sum to 0, so the centroids drop out):  dE_g / dx[dst_i] += 2 (q_i - R_g p_i),  dE_g / dx[src_i] += -2 R_g^T (q_i - R_g p_i)
+ * `var` is one float in device memory; the likelihood is left unnormalised.  A weight of 0 switches its generator off (energy and
+ * force; the report still describes it).  The generators arrive as one per-residue table in device memory, partner int32 [G, 2, N]:
+ * partner[g][0][i] is the residue i maps to as a source, partner[g][1][i] the residue that maps to i, -1 for none.  The caller
+ * validates it (each row the inverse of the other); entries index LDS, so the kernel clamps them into 0..N-1 all the same.
+ * report_out[b] holds GENIE_SYMMETRY_REPORT floats:
+ *   e_symmetry (weight0 E_0 + weight1 E_1, before the division by 2 var), symmetry_rmsd (sqrt(sum_g E_g / sum_g L_g), unweighted),
+ *   then per generator slot g = 0, 1: rmsd_g (sqrt(E_g / L_g)), angle_g (the rotation angle of R_g in degrees, in [0, 180], as
+ *   2 atan2(|v|, |w|) of the quaternion (w, v): a two-fold has a symmetric correlation and sits at exactly 180 or 0, where acos has no
+ *   digits), rise_g (|u_g . (c_d - R_g c_s)| in Angstrom, u_g the rotation axis; |c_d - R_g c_s| when the angle is 0; R_g fixes u_g, so
+ *   it is evaluated as |u_g . (c_d - c_s)|)
+ * an unused slot reports zeros.  For a closed C_n the angle tends to 360 / n and the rise to 0; for a repeat they are its twist and
+ * rise.  Coincident or collinear residues have a degenerate largest eigenvalue: every output stays finite, E_g is still the minimum,
+ * the rotation (angle, rise, gradient) is one of the equally good ones.  logp_out and grad_out are given together or both NULL;
+ * report_out may be NULL; at least one output is asked for.
+ * One launch on `stream`: grid B, 256 threads; the work-group of particle b stages x0[b] in LDS (12 N + 320 bytes) and makes three
+ * passes over the residues, both generators in each: the centroids (c_d as c_s plus the mean of x[dst] - x[src]), the correlation,
+ * then -- after wave g has solved the 4x4 eigenproblem of generator g, wave-uniform work -- the residuals, E_g and the gradient of
+ * every residue as a gather through the table (a residue has at most one source and one destination role per generator).  Every sum
+ * is a butterfly inside a wave and the four wave results in wave order.  No allocation, no synchronisation, no host read, no
+ * atomics, no scatter: two calls on the same inputs are bitwise equal.  Nothing passes through memory between the passes, so
+ * genie_symmetry_potential_work_bytes(B, N) is 0 and `work` may be NULL; the pair is taken so that every potential is called alike.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 1; x0, partner or var NULL; G outside 1..2; a negative or non-finite weight; no output asked for; logp_out and
+ * grad_out not given together; `work` NULL with work_bytes above 0; an N whose staging does not fit in LDS (160 KiB: N above 13 626). */
+#define GENIE_SYMMETRY_REPORT 8   /* e_symmetry, symmetry_rmsd, rmsd_0, angle_0, rise_0, rmsd_1, angle_1, rise_1 */
+#define GENIE_SYMMETRY_MAX_GENERATORS 2
+int genie_symmetry_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int G,
+                             const int32_t* partner /*[G,2,N], device*/, float weight0, float weight1,
+                             const float* var /*[1], device*/, float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                             float* report_out /*[B,GENIE_SYMMETRY_REPORT] or NULL*/, void* work, size_t work_bytes);
+size_t genie_symmetry_potential_work_bytes(int B, int N);
 
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
