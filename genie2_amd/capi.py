@@ -120,6 +120,9 @@ SYMBOLS = {
     'genie_symmetry_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float] +
                                  [C.c_void_p] * 5 + [C.c_size_t]),
     'genie_symmetry_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'genie_binder_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 8 +
+                               [C.c_void_p] * 6 + [C.c_size_t]),
+    'genie_binder_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -140,6 +143,11 @@ SHEET_PARALLEL, SHEET_RUNG = 1 << 29, 1 << 30       # GENIE_SHEET_PARALLEL, GENI
 
 SYMMETRY_REPORT = ('e_symmetry', 'symmetry_rmsd', 'rmsd_0', 'angle_0', 'rise_0', 'rmsd_1', 'angle_1', 'rise_1')      # GENIE_SYMMETRY_REPORT slots
 SYMMETRY_MAX_GENERATORS = 2     # GENIE_SYMMETRY_MAX_GENERATORS
+
+BINDER_REPORT = ('contacts', 'n_contacts', 'n_interface', 'target_min_distance', 'n_target_clash', 'n_hotspots_contacted', 'e_target_clash',
+                 'e_contact', 'e_hotspot')      # GENIE_BINDER_REPORT slots
+BINDER_COUNTS = ('n_contacts', 'n_interface', 'n_target_clash', 'n_hotspots_contacted')
+BINDER_MAX_HOTSPOTS = 64        # GENIE_BINDER_MAX_HOTSPOTS
 
 _lib = None
 

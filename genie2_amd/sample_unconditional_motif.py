@@ -40,13 +40,19 @@ writes outdir/sheet/{length}_{index}.txt as that CLI does, and lengths that cann
 
 `--symmetry C<n>|D<n>|R<n>` (with `--unit_length`, `--unit_linker`, `--unit_offset`, `--symmetry_weight`, `--symmetry_tausq`,
 `--unit_chains` and `--write_symmetry`: the flags of add_symmetry_arguments in the same module) adds symmetry guidance, summed last;
-`--write_symmetry` writes outdir/symmetry/{length}_{index}.txt as that CLI does, and lengths the layout does not fit are skipped."""
+`--write_symmetry` writes outdir/symmetry/{length}_{index}.txt as that CLI does, and lengths the layout does not fit are skipped.
+
+`--target_pdb` (with `--target_chains`, `--hotspots`, `--hotspot_contacts`, `--hotspot_weight`, `--contact_distance`, `--contacts_min`,
+`--contacts_max`, `--contacts_weight`, `--target_clash_distance`, `--target_clash_weight`, `--target_standoff`, `--binder_tausq`,
+`--write_binder` and `--write_complex`: the flags of add_binder_arguments in the same module) adds binder guidance against a fixed
+target, summed after all the others; `--write_binder` writes outdir/binder/{length}_{index}.txt and `--write_complex`
+outdir/complex/{length}_{index}.pdb as that CLI does."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import (GuidedRunner, add_guidance_arguments, add_secstruct_arguments, add_shape_arguments,
-                                         add_sheet_arguments, add_symmetry_arguments)
+from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_guidance_arguments, add_secstruct_arguments,
+                                         add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
 
 
 def load_motif_segments(filepath):
@@ -143,6 +149,7 @@ def build_parser():
     add_secstruct_arguments(p)
     add_sheet_arguments(p)
     add_symmetry_arguments(p)
+    add_binder_arguments(p)
     return p
 
 

@@ -2,7 +2,7 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure, sheet or symmetry term (below), is needed.
+least one of the three, or a secondary-structure, sheet, symmetry or binder term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -35,9 +35,26 @@ skipped.  `--unit_chains` samples and writes the units as chains A, B, ... (no l
 one `key value` line per field of SymmetryPotential.describe.  Units can satisfy the term by lying on top of each other, which
 `--clash_distance` prevents; `--rog_max` over the assembly keeps separate chains together.
 
+`--target_pdb FILE` guides the design relative to a structure that is not sampled: a BinderPotential (csrc/binder_kernels.hip) over
+the C-alpha atoms of the file's chains (`--target_chains AB`: those chains only), summed after everything else and enough on its own.
+`--hotspots A45,A46,B12` (chain letter and residue number; or a file of such tokens, `#` starting a comment) asks every listed target
+residue for `--hotspot_contacts` soft contacts with the design (weight `--hotspot_weight`); `--contacts_min` / `--contacts_max` keep
+the soft number of design-target contacts within `--contact_distance` (default 8 A) in a range (weight `--contacts_weight`; only a
+max leaves the min at 0, only a min leaves the count unbounded above); `--target_clash_distance` pushes design-target pairs closer
+than that apart (weight `--target_clash_weight`).  At least one of the three is needed with a target.  `--target_standoff D` moves
+the target, without rotating it, so that the origin -- where designs are born -- lies D Angstrom outside the hotspot patch on the
+line from the target's centroid through the hotspots'; without it the file's frame is used as it is.  `--binder_tausq` is the
+likelihood variance.  `--write_binder` adds outdir/binder/{length}_{index}.txt: a line `hotspot A45 0.873` per hotspot (its soft
+contacts with the written design), then one `key value` line per field of BinderPotential.describe.  `--write_complex` adds
+outdir/complex/{length}_{index}.pdb: the target's chains followed by the design as the last chain, centred jointly, relative
+placement kept (the files under pdbs/ are centred per design); residue numbers restart at 1 in every chain.  A binder flag without
+`--target_pdb` ends the run.  Not built: rotating the target, per-design-residue interface masks, all-atom or side-chain terms, and
+feeding the target to the denoiser.
+
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
-add_shape_arguments, add_secstruct_arguments, add_sheet_arguments and add_symmetry_arguments too and then guides with the sum of the potentials asked for."""
+add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments and add_binder_arguments too and then guides
+with the sum of the potentials asked for."""
 import os
 
 from tqdm import tqdm
@@ -50,6 +67,9 @@ SECSTRUCT_KEYS = ('helix_weight', 'extended_weight', 'ss_target_weight', 'ss_tau
 SECSTRUCT_COUNTS = ('n_helix', 'n_extended', 'n_target_missed')
 SHEET_KEYS = ('antiparallel_weight', 'parallel_weight', 'ladder_weight', 'sheet_tausq')
 SYMMETRY_KEYS = ('symmetry', 'unit_length', 'unit_linker', 'unit_offset', 'symmetry_weight', 'symmetry_tausq')
+BINDER_DEFAULTS = dict(target_pdb=None, target_chains=None, hotspots=None, hotspot_contacts=1.0, hotspot_weight=1.0, contact_distance=8.0,
+                       contacts_min=None, contacts_max=None, contacts_weight=1.0, target_clash_distance=None, target_clash_weight=1.0,
+                       target_standoff=None, binder_tausq=1.0, write_binder=False, write_complex=False)
 
 
 def add_shape_arguments(parser):
@@ -345,6 +365,117 @@ def write_symmetry_report(report, header, directory, length, offset):
     write_report(report, (), directory, length, offset, [header] * len(next(iter(report.values()))))
 
 
+def add_binder_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    parser.add_argument('--target_pdb', type=str, default=None,
+                        help='Guide the design relative to the C-alpha atoms of this structure, which is not sampled; default: no such '
+                             'term' + tail)
+    parser.add_argument('--target_chains', type=str, default=None, help='Chain letters of the target to use, e.g. AB; default: all' + tail)
+    parser.add_argument('--hotspots', type=str, default=None,
+                        help='Target residues the design must touch, e.g. A45,A46,B12 (chain letter and residue number), or a file of '
+                             'such tokens' + tail)
+    parser.add_argument('--hotspot_contacts', type=float, default=1.0, help='Soft contacts asked of every hotspot' + tail)
+    parser.add_argument('--hotspot_weight', type=float, default=1.0, help='Weight of the hotspot term' + tail)
+    parser.add_argument('--contact_distance', type=float, default=8.0,
+                        help='C-alpha distance in Angstrom at which a design-target pair counts half a contact' + tail)
+    parser.add_argument('--contacts_min', type=float, default=None,
+                        help='Guide the soft number of design-target contacts above this; default: no such bound' + tail)
+    parser.add_argument('--contacts_max', type=float, default=None,
+                        help='Guide the soft number of design-target contacts below this; default: no such bound' + tail)
+    parser.add_argument('--contacts_weight', type=float, default=1.0, help='Weight of the contact-count term' + tail)
+    parser.add_argument('--target_clash_distance', type=float, default=None,
+                        help='Guide design-target C-alpha pairs apart that are closer than this many Angstrom; default: no such '
+                             'term' + tail)
+    parser.add_argument('--target_clash_weight', type=float, default=1.0, help='Weight of the target clash term' + tail)
+    parser.add_argument('--target_standoff', type=float, default=None,
+                        help='Move the target (no rotation) so that the origin, where designs are born, lies this many Angstrom outside '
+                             'the hotspot patch; default: the frame of the file' + tail)
+    parser.add_argument('--binder_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the binder terms, Angstrom^2' + tail)
+    parser.add_argument('--write_binder', action='store_true',
+                        help='Write outdir/binder/{length}_{index}.txt: the soft contacts of every hotspot, then contacts, interface '
+                             'size, closest approach, clashes and energies of every written structure' + tail)
+    parser.add_argument('--write_complex', action='store_true',
+                        help='Write outdir/complex/{length}_{index}.pdb: the target chains and the design as the last chain, placed as '
+                             'sampled' + tail)
+
+
+def binder_constants(params):
+    """The binder keys of a runner's constants: the flags of add_binder_arguments; with --target_pdb also 'target', the file read,
+    placed (--target_standoff) and ready to travel to a worker process -- 'xyz' float64 numpy [M, 3] in the sampler's frame, 'labels',
+    'chain_lengths', 'aatype' numpy [M], 'hotspots' (indices) -- and 'contacts' = (min, max) or None (one of the two given: the other
+    is 0 / inf).  A binder flag without --target_pdb, a target with no term, and a file, chain, hotspot or standoff that does not
+    hold up end the run here."""
+    import math
+    from .smc import load_target, parse_hotspots, place_target
+    c = {k: params.get(k, v) for k, v in BINDER_DEFAULTS.items()}
+    c['write_binder'], c['write_complex'] = bool(c['write_binder']), bool(c['write_complex'])
+    c['target'] = c['contacts'] = None
+    if c['target_pdb'] is None:
+        given = [k for k, v in BINDER_DEFAULTS.items() if c[k] != v]
+        if given:
+            raise SystemExit('%s: a binder flag needs --target_pdb, the structure it is about' % ', '.join('--' + k for k in given))
+        return c
+    lo, hi = c['contacts_min'], c['contacts_max']
+    c['contacts'] = None if lo is None and hi is None else (0.0 if lo is None else lo, math.inf if hi is None else hi)
+    if c['hotspots'] is None and c['contacts'] is None and c['target_clash_distance'] is None:
+        raise SystemExit('--target_pdb needs a term: --hotspots, --contacts_min, --contacts_max or --target_clash_distance')
+    try:
+        xyz, labels, chain_lengths, aatype = load_target(c['target_pdb'], c['target_chains'])
+        hotspots = parse_hotspots(c['hotspots'], labels) if c['hotspots'] is not None else []
+        xyz = place_target(xyz, hotspots, c['target_standoff'])
+    except (OSError, ValueError) as e:
+        raise SystemExit('--target_pdb / --hotspots / --target_standoff: %s' % e) from None
+    c['target'] = dict(xyz=xyz.numpy(), labels=labels, chain_lengths=chain_lengths, aatype=aatype.numpy(), hotspots=hotspots)
+    return c
+
+
+def has_binder_terms(constants):
+    return constants.get('target') is not None
+
+
+def binder_potential(constants, length, abar, device):
+    """The BinderPotential the constants ask for at this length, or None when they name no target."""
+    if not has_binder_terms(constants):
+        return None
+    from .smc import BinderPotential
+    t = constants['target']
+    return BinderPotential(length, abar, t['xyz'], hotspots=t['hotspots'] or None, clash_distance=constants['target_clash_distance'],
+                           clash_weight=constants['target_clash_weight'], contact_distance=constants['contact_distance'],
+                           contacts=constants['contacts'], contacts_weight=constants['contacts_weight'],
+                           hotspot_contacts=constants['hotspot_contacts'], hotspot_weight=constants['hotspot_weight'],
+                           tausq=constants['binder_tausq'], device=device)
+
+
+def hotspot_names(target):
+    """The hotspots of binder_constants' target as the CLI names them: A45, B12, ..."""
+    return ['{}{}'.format(*target['labels'][h]) for h in target['hotspots']]
+
+
+def write_binder_report(hotspot_contacts, names, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a line `hotspot A45 0.873` per hotspot (`names`, and row i of
+    `hotspot_contacts` [rows, H], BinderPotential.hotspot_contacts_of of TwistedSampler.last_positions), then a `key value` line per
+    field of `report` (the binder fields of last_shape), %.3f for contacts, distances and energies, %d for counts."""
+    from .capi import BINDER_COUNTS
+    rows = hotspot_contacts.tolist()
+    write_report(report, BINDER_COUNTS, directory, length, offset,
+                 ['\n'.join('hotspot {} {:.3f}'.format(n, v) for n, v in zip(names, row)) for row in rows])
+
+
+def write_complex(positions, target, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.pdb, through save_np_features_to_pdb: the target's chains (binder_constants'
+    target: coordinates in the sampler's frame, residue types from its file) followed by the design, row i of `positions` [rows, N, 3]
+    (TwistedSampler.last_positions), as the last chain.  The writer centres the complex as a whole, so relative placement is kept."""
+    import numpy as np
+    from . import features as F
+    os.makedirs(directory, exist_ok=True)
+    M = len(target['xyz'])
+    for i, design in enumerate(np.asarray(positions, dtype=float)):
+        f = F.create_empty_np_features(list(target['chain_lengths']) + [len(design)])
+        f['aatype'][np.arange(M), np.asarray(target['aatype'])] = 1
+        f['atom_positions'] = np.concatenate([np.asarray(target['xyz'], dtype=float), design])
+        F.save_np_features_to_pdb(f, os.path.join(directory, '{}_{}.pdb'.format(length, offset + i)))
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -389,8 +520,8 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet and symmetry potentials the constants ask
-    for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, symmetry and binder potentials the
+    constants ask for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
 
     def guided_lengths(self, tasks, params):
         """The tasks whose length the restraints, the blueprint, the ladder and the symmetric layout allow."""
@@ -408,6 +539,7 @@ class GuidedRunner(UnconditionalRunner):
         c.update(secstruct_constants(params))
         c.update(sheet_constants(params))
         c.update(symmetry_constants(params))
+        c.update(binder_constants(params))
         return c
 
     def batch_potentials(self, constants, length, abar, device):
@@ -430,13 +562,14 @@ class GuidedRunner(UnconditionalRunner):
             secstruct = secstruct_potential(constants, length, abar, device)
             sheet = sheet_potential(constants, length, abar, device)
             symmetry = symmetry_potential(constants, length, abar, device)
+            binder = binder_potential(constants, length, abar, device)
             chains = {'chain_lengths': symmetry.chain_lengths()} if constants['unit_chains'] else {}
             for batch, offset in self.batches(constants, outdir, length):
                 sampler.sample({
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
                     'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet,
-                                                        symmetry),
+                                                        symmetry, binder),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **chains, **self.partial_params(constants)})
@@ -455,15 +588,22 @@ class GuidedRunner(UnconditionalRunner):
                 if constants['write_symmetry'] and symmetry is not None:
                     write_symmetry_report(report_fields(sampler.last_shape, capi.SYMMETRY_REPORT), symmetry_header(symmetry),
                                           os.path.join(outdir, 'symmetry'), length, offset)
+                if constants['write_binder'] and binder is not None:
+                    write_binder_report(binder.hotspot_contacts_of(sampler.last_positions.to(binder.device)).cpu(),
+                                        hotspot_names(constants['target']), report_fields(sampler.last_shape, capi.BINDER_REPORT),
+                                        os.path.join(outdir, 'binder'), length, offset)
+                if constants['write_complex'] and binder is not None:
+                    write_complex(sampler.last_positions.numpy(), constants['target'], os.path.join(outdir, 'complex'), length, offset)
 
 
 class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
-        if not has_shape_terms(c) and not has_secstruct_terms(c) and not has_sheet_terms(c) and not has_symmetry_terms(c):
+        if not (has_shape_terms(c) or has_secstruct_terms(c) or has_sheet_terms(c) or has_symmetry_terms(c) or has_binder_terms(c)):
             raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
                              'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target), a sheet term '
-                             '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file) or --symmetry')
+                             '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file), a binder term (--target_pdb '
+                             'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance) or --symmetry')
         return c
 
 
@@ -475,6 +615,7 @@ def build_parser():
     add_secstruct_arguments(p)
     add_sheet_arguments(p)
     add_symmetry_arguments(p)
+    add_binder_arguments(p)
     return p
 
 

@@ -8,7 +8,8 @@ gyration, clashes, distance restraints; not in the reference) is the second buil
 (csrc/secstruct_kernels.hip: helix / extended content and a blueprint; the reference's sampler/secstruct.py runs P-SEA on the host and
 is not differentiable) the third, SheetPotential (csrc/sheet_kernels.hip: antiparallel / parallel strand pairing and a ladder of listed
 rungs; not in the reference) the fourth, SymmetryPotential (csrc/symmetry_kernels.hip: cyclic, dihedral and repeat symmetry by
-superposing units under the group's generators; not in the reference) the fifth, and SumPotential adds potentials.
+superposing units under the group's generators; not in the reference) the fifth, BinderPotential (csrc/binder_kernels.hip: contacts,
+hotspot coverage and clashes against a fixed target that is not sampled; not in the reference) the sixth, and SumPotential adds potentials.
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -136,9 +137,11 @@ class TwistedSampler(UnconditionalSampler):
     or None when it has no `locate`; `last_shape` what its `describe` says of them (ShapePotential.describe: 'rog', 'min_distance',
     'n_clash', 'e_rog', 'e_clash', 'e_restraint', 'n_violated', 'max_violation' as CPU tensors, one row per returned sample; with a
     SecStructPotential its eight fields, with a SheetPotential its nine, with a SymmetryPotential its eight, and with a SumPotential
-    every member's), or None when it has no `describe`; `last_secstruct` what its `assign` says of them (SecStructPotential.assign: int8 [rows, N] on the CPU, 0 C, 1 H, 2 E), or None when it has no
+    every member's; with a BinderPotential its nine), or None when it has no `describe`; `last_secstruct` what its `assign` says of them (SecStructPotential.assign: int8 [rows, N] on the CPU, 0 C, 1 H, 2 E), or None when it has no
     `assign`; `last_pairs` what its `pairs` says of them (SheetPotential.pairs: int32 [rows, N, 2] on the CPU, every residue's
-    antiparallel and parallel partner, -1 for none), or None when it has no `pairs`.
+    antiparallel and parallel partner, -1 for none), or None when it has no `pairs`; `last_positions` the returned coordinates
+    themselves in the sampler's frame, a CPU float32 [rows, N, 3] tensor (the written PDBs are centred per design, so this is what
+    puts a design next to a BinderPotential's target).
     Optional 'num_steps' = K (not in the reference) visits the K timesteps of pack.respaced_steps with the ancestral kernel between
     them (pack.twisted_coefficients): `ess_trace` then has K - 1 entries, the last visited step takes the role of step 1, and
     `last_unguided_steps` and the potential keep reading the timestep itself.  'sampler': 'ddim' is refused (ValueError): the
@@ -238,7 +241,7 @@ class TwistedSampler(UnconditionalSampler):
 
     def _finish(self, st, trans, feats, start):
         """The reports on the returned coordinates `trans` (MotifPotential.locate: the best placement of every sample and its
-        superposed RMSD; describe; assign; the RMSD to `start`) and the features to write."""
+        superposed RMSD; describe; assign; the RMSD to `start`; the coordinates themselves as last_positions) and the features to write."""
         twist = st.twist
         self.last_fit = None
         if hasattr(twist, 'locate') and getattr(twist, 'has_fit', True):
@@ -247,6 +250,7 @@ class TwistedSampler(UnconditionalSampler):
         self.last_secstruct = twist.assign(trans).cpu() if hasattr(twist, 'assign') else None
         self.last_pairs = twist.pairs(trans).cpu() if hasattr(twist, 'pairs') else None
         feats['atom_positions'] = trans.cpu()
+        self.last_positions = feats['atom_positions'].detach().to(torch.float32)
         self.last_start_rmsd = None if start is None else start_rmsd(feats['atom_positions'], start, feats['residue_mask'])
         return F.debatchify_np_features(F.convert_tensor_features_to_numpy(feats))
 
@@ -1257,6 +1261,210 @@ class SymmetryPotential(_HipPotential):
         w = [self.weight * v for v in self.generator_weights] + [0.0]
         self._call('genie_symmetry_potential', self._stream(), B, self.n_res, _ptr(x), self.G, _ptr(self.partner), w[0], w[1], _ptr(var),
                    *(_ptr(t) for t in outs), *self._workspace(self.lib.genie_symmetry_potential_work_bytes(B, self.n_res)))
+        return tuple(t for t in outs if t is not None)
+
+
+def load_target(path, chains=None):
+    """The fixed target of a BinderPotential from a PDB file (plain or .gz): the C-alpha atoms of the chains named in `chains` (a
+    string of chain letters such as 'AB'; None: every chain), in file order, as (xyz float64 [M, 3] in the file's frame, labels
+    [(chain, resseq), ...] one per residue, chain_lengths [one per run of a chain letter], aatype int64 [M] residue-type indices in
+    features.RESTYPES' order, 0 (ALA) for a residue name outside the twenty).  features.parse_pdb drops the residue numbers a hotspot
+    is named by, so this is a reader of its own over the same columns.  A file with no C-alpha atom of the chosen chains, and a chosen
+    chain the file does not have, are ValueErrors."""
+    import gzip
+    from .features import RESTYPE_ORDER, _RESTYPE_3_TO_1
+    if chains is not None and (not isinstance(chains, str) or not chains or len(set(chains)) != len(chains)):
+        raise ValueError('chains must be a string of distinct chain letters such as "AB", got %r' % (chains,))
+    xyz, labels, lengths, aatype, current, seen = [], [], [], [], None, set()
+    with (gzip.open(path, 'rt') if str(path).endswith('.gz') else open(path, 'r')) as fh:
+        for line in fh:
+            if not (line.startswith('ATOM') and line[13:15].strip() == 'CA'):
+                continue
+            chain = line[21]
+            seen.add(chain)
+            if chains is not None and chain not in chains:
+                current = None
+                continue
+            if chain != current:
+                lengths.append(0)
+                current = chain
+            lengths[-1] += 1
+            labels.append((chain, int(line[22:26])))
+            aatype.append(RESTYPE_ORDER.get(_RESTYPE_3_TO_1.get(line[17:20], 'A'), 0))
+            xyz.append([float(line[30:38]), float(line[38:46]), float(line[46:54])])
+    missing = [c for c in (chains or '') if c not in seen]
+    if missing:
+        raise ValueError('%s has no C-alpha atom of chain(s) %s (it has %s)' % (path, ', '.join(missing), ', '.join(sorted(seen)) or 'none'))
+    if not xyz:
+        raise ValueError('%s has no C-alpha ATOM record' % (path,))
+    return torch.tensor(xyz, dtype=torch.float64), labels, lengths, torch.tensor(aatype, dtype=torch.int64)
+
+
+def parse_hotspots(spec, labels):
+    """Hotspot residues named by chain letter and residue number, `A45,A46,B12` (commas or whitespace between tokens), or a file of
+    such tokens in which `#` starts a comment -> their sorted distinct indices into `labels` (load_target's).  A token that names no
+    residue of the target, that names more than one, that does not parse or that is given twice is a ValueError naming it; so are
+    more than capi.BINDER_MAX_HOTSPOTS of them."""
+    import os
+    import re
+    if not isinstance(spec, str):
+        raise ValueError('hotspots must be a string such as "A45,A46" or a file of such tokens, got %r' % (spec,))
+    if os.path.isfile(spec):
+        with open(spec) as fh:
+            spec = ' '.join(line.split('#', 1)[0] for line in fh)
+    index, out = {}, []
+    for i, label in enumerate(labels):
+        index.setdefault((label[0], int(label[1])), []).append(i)
+    for token in [t for t in re.split(r'[,\s]+', spec) if t]:
+        m = re.fullmatch(r'(\S)(-?\d+)', token)
+        if m is None:
+            raise ValueError('hotspot %r is not a chain letter followed by a residue number' % token)
+        found = index.get((m.group(1), int(m.group(2))), [])
+        if len(found) != 1:
+            raise ValueError('hotspot %r names %s residue of the target' % (token, 'no' if not found else 'more than one'))
+        if found[0] in out:
+            raise ValueError('hotspot %r is given twice' % token)
+        out.append(found[0])
+    if len(out) > capi.BINDER_MAX_HOTSPOTS:
+        raise ValueError('at most %d hotspots, got %d' % (capi.BINDER_MAX_HOTSPOTS, len(out)))
+    return sorted(out)
+
+
+def place_target(xyz, hotspots, standoff):
+    """The target moved, by a pure translation, so that the sampler's origin -- where designs are born -- lies `standoff` Angstrom
+    outside the hotspot patch: with t the target's centroid, h the hotspots' and u = (h - t) / |h - t|, every atom moves by
+    -(h + standoff u).  The hotspot centroid then sits at -standoff u and the target's behind it on the same ray.  No rotation.
+    `standoff=None` leaves the file's frame alone (a float64 copy).  No hotspots, |h - t| < 1e-3 A (no direction to step out in) and a
+    negative or non-finite standoff are ValueErrors."""
+    import math
+    xyz = torch.as_tensor(xyz, dtype=torch.float64).clone()
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError('the target must be [M, 3] with M >= 1, got %s' % (tuple(xyz.shape),))
+    if standoff is None:
+        return xyz
+    if not (math.isfinite(float(standoff)) and float(standoff) >= 0):
+        raise ValueError('standoff must be finite and >= 0, got %r' % (standoff,))
+    hotspots = list(hotspots) if hotspots is not None else []
+    if not hotspots:
+        raise ValueError('a standoff needs hotspots: they say on which side of the target the design starts')
+    t, h = xyz.mean(dim=0), xyz[hotspots].mean(dim=0)
+    gap = float((h - t).norm())
+    if gap < 1e-3:
+        raise ValueError('the hotspot centroid is %.1e A from the target centroid: no direction to step out in' % gap)
+    return xyz - (h + float(standoff) * (h - t) / gap)
+
+
+def check_hotspots(hotspots, n_target):
+    """Hotspot indices as a sorted list of distinct integers in 0..n_target-1, at most capi.BINDER_MAX_HOTSPOTS of them; a ValueError
+    otherwise."""
+    try:
+        out = [h for h in (hotspots.tolist() if torch.is_tensor(hotspots) else list(hotspots if hotspots is not None else []))]
+    except TypeError:
+        raise ValueError('hotspots must be a list of target indices, got %r' % (hotspots,)) from None
+    for h in out:
+        if isinstance(h, bool) or not isinstance(h, numbers.Integral) or not 0 <= h < n_target:
+            raise ValueError('hotspot %r is not an integer in 0..%d' % (h, n_target - 1))
+    if len(set(out)) != len(out):
+        raise ValueError('a hotspot is listed twice: %r' % (out,))
+    if len(out) > capi.BINDER_MAX_HOTSPOTS:
+        raise ValueError('at most %d hotspots, got %d' % (capi.BINDER_MAX_HOTSPOTS, len(out)))
+    return sorted(int(h) for h in out)
+
+
+BINDER_MAX_TARGET = 12714       # the longest target whose staging fits in the kernel's 160 KiB of LDS (include/genie_hip.h)
+
+
+class BinderPotential(_HipPotential):
+    """Binder guidance as one HIP pass (genie_binder_potential, csrc/binder_kernels.hip; include/genie_hip.h states the mathematics):
+    `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside the other
+    built-in potentials (SumPotential adds them).  It is the one potential that looks at something that is not being sampled:
+    `target` [M, 3], fixed C-alpha coordinates in the frame the sampler works in (load_target reads them from a file, place_target
+    moves them so that the origin, where designs are born, faces the hotspots).  Three terms, each a squared hinge:
+      clash_distance   every design-target pair closer than this many Angstrom (None: off), weighted clash_weight;
+      contacts         (min, max): the soft number of contacts C = sum over pairs of 1 / (1 + (d / contact_distance)^6) is kept in
+                       that range (None: off; max may be inf), weighted contacts_weight;
+      hotspots         target indices (None or empty: off): each hotspot's own soft contacts c_h, summed over the design, are kept
+                       at or above hotspot_contacts, weighted hotspot_weight.
+    log p = -(E_clash + E_contact + E_hot) / (2 var), var = xstart_variance(alphas_cumprod[step], tausq) computed on the device, so
+    nothing on the per-step path reads device memory from the host; the forward keeps the gradient the kernel computes and the
+    backward scales it.  The likelihood is unnormalised.
+
+    Everything is validated on the host before the device is looked at; a potential with no term enabled is a ValueError.  The target
+    and the hotspot list are uploaded once.  `describe(x)` reports every sample of x with the names of capi.BINDER_REPORT: 'contacts'
+    (C), 'n_contacts' (pairs closer than contact_distance), 'n_interface' (design residues in such a pair), 'target_min_distance',
+    'n_target_clash' (pairs closer than clash_distance), 'n_hotspots_contacted' (int64 counts), 'e_target_clash', 'e_contact',
+    'e_hotspot' (the weighted energies, before the division by 2 var): [B] tensors on the potential's device.
+    `hotspot_contacts_of(x)` is [B, H], the c_h in the order of `hotspots` (ascending target index).
+
+    The defaults (tausq = 1 A^2, contact_distance 8 A, one soft contact per hotspot, weights 1) are design choices: no trained
+    checkpoint is in the tree, so their effect on sample quality is unmeasured.  The target does not rotate, no design residue is
+    exempt from or singled out for the interface, only C-alpha atoms are seen, and the denoiser never sees the target."""
+
+    def __init__(self, n_res, alphas_cumprod, target, hotspots=None, clash_distance=None, clash_weight=1.0, contact_distance=8.0,
+                 contacts=None, contacts_weight=1.0, hotspot_contacts=1.0, hotspot_weight=1.0, tausq=1.0, device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or n_res < 1:
+            raise ValueError('n_res must be an integer >= 1, got %r' % (n_res,))
+        try:
+            y = torch.as_tensor(target).detach().to(dtype=torch.float32, device='cpu')
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('target must be [M, 3] coordinates, got %r' % (type(target),)) from None
+        if y.dim() != 2 or y.shape[1] != 3 or y.shape[0] < 1:
+            raise ValueError('target must be [M, 3] with M >= 1, got %s' % (tuple(y.shape),))
+        if y.shape[0] > BINDER_MAX_TARGET:
+            raise ValueError('target has %d residues, at most %d fit in the LDS of the kernel' % (y.shape[0], BINDER_MAX_TARGET))
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError('target has a coordinate that is not finite')
+        self.hotspots = check_hotspots(hotspots, int(y.shape[0]))
+        for name, v in (('clash_distance', clash_distance), ('clash_weight', clash_weight), ('contact_distance', contact_distance),
+                        ('contacts_weight', contacts_weight), ('hotspot_contacts', hotspot_contacts), ('hotspot_weight', hotspot_weight)):
+            if v is not None and not (_is_scalar(v) and math.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, v))
+        if contact_distance is None or not float(contact_distance) > 0:
+            raise ValueError('contact_distance must be > 0, got %r' % (contact_distance,))
+        if contacts is not None:
+            try:
+                lo, hi = (float(v) for v in contacts)
+            except (TypeError, ValueError):
+                raise ValueError('contacts must be (min, max), got %r' % (contacts,)) from None
+            if not (math.isfinite(lo) and lo >= 0 and hi >= lo):
+                raise ValueError('contacts must be (min, max) with 0 <= min <= max, min finite, got %r' % (contacts,))
+        if not (_is_scalar(tausq) and math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        if clash_distance is None and contacts is None and not self.hotspots:
+            raise ValueError('no term enabled: give clash_distance, contacts or hotspots')
+        # a term that is off is a weight of 0 to the entry
+        self.clash_distance, self.clash_weight = (0.0, 0.0) if clash_distance is None else (float(clash_distance), float(clash_weight))
+        self.contact_distance = float(contact_distance)
+        self.contacts, self.contacts_weight = ((0.0, math.inf), 0.0) if contacts is None else ((lo, hi), float(contacts_weight))
+        self.hotspot_contacts, self.hotspot_weight = float(hotspot_contacts), float(hotspot_weight) if self.hotspots else 0.0
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.M, self.H = int(y.shape[0]), len(self.hotspots)
+        self.target = y.contiguous().to(self.device)
+        self.hotspot_index = torch.tensor(self.hotspots, dtype=torch.int32).to(self.device) if self.H else None
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, want='report')               # (the energies do not depend on var)
+        return _decode_report(report, capi.BINDER_REPORT, capi.BINDER_COUNTS)
+
+    def hotspot_contacts_of(self, x):
+        """[B, H] float32 on the potential's device: every hotspot's soft contacts c_h with every sample of x [B,N,3]."""
+        x = self._checked(x)
+        if not self.H:
+            return torch.zeros(x.shape[0], 0, dtype=torch.float32, device=x.device)
+        return self._launch(x, self._one, want='hotspots')[0]
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous): (logp, grad), (report [B, 9],) or (hotspot_out [B, H],) as `want` says."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        outs = {'logp': lambda: [torch.empty(B, **f32), torch.empty_like(x), None, None],
+                'report': lambda: [None, None, torch.empty(B, len(capi.BINDER_REPORT), **f32), None],
+                'hotspots': lambda: [None, None, None, torch.empty(B, self.H, **f32)]}[want]()
+        self._call('genie_binder_potential', self._stream(), B, self.n_res, _ptr(x), self.M, _ptr(self.target), self.H,
+                   _ptr(self.hotspot_index), self.clash_distance, self.clash_weight, self.contact_distance, self.contacts[0],
+                   self.contacts[1], self.contacts_weight, self.hotspot_contacts, self.hotspot_weight, _ptr(var),
+                   *(_ptr(t) for t in outs), *self._workspace(self.lib.genie_binder_potential_work_bytes(B, self.n_res, self.H)))
         return tuple(t for t in outs if t is not None)
 
 

@@ -457,6 +457,63 @@ int genie_symmetry_potential(genie_stream_t stream, int B, int N, const float* x
                              float* report_out /*[B,GENIE_SYMMETRY_REPORT] or NULL*/, void* work, size_t work_bytes);
 size_t genie_symmetry_potential_work_bytes(int B, int N);
 
+/* The binder potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle: how a
+ * design sits against a structure that is not being sampled (csrc/binder_kernels.hip) -- a receptor to bind, a hotspot patch to
+ * cover, a partner to stay clear of.  Every other built-in potential looks at the design alone, and the denoiser has no input for an
+ * external chain, so guidance is the only way to ask for this.  The reference has no counterpart.
+ * The target is y_m, m = 0..M-1: C-alpha coordinates in Angstrom, fixed, in the frame the sampler works in (device memory, [M,3]).
+ * hotspot is a list of H distinct target indices, ascending (device int32; H may be 0).  For particle b with coordinates x_n,
+ * n = 0..N-1 (all N rows are used):
+ *   d_nm = |x_n - y_m|
+ *   s(d) = 1 / (1 + (d / contact_distance)^6)        (a rational switch, computed from d^2: no square root, no exp)
+ *   E_clash   = clash_weight    * sum_{n,m} max(0, clash_distance - d_nm)^2
+ *   C         = sum_{n,m} s(d_nm)
+ *   E_contact = contacts_weight * ( max(0, contacts_min - C)^2 + max(0, C - contacts_max)^2 )     (contacts_max may be +inf)
+ *   c_h       = sum_n s(d_{n,hotspot[h]})
+ *   E_hot     = hotspot_weight  * sum_h max(0, hotspot_contacts - c_h)^2
+ *   logp_out[b] = -(E_clash + E_contact + E_hot) / (2 var)
+ *   grad_out[b,n] = d logp[b] / d x_n, analytic: with r = d / contact_distance, ds/dx_n = -6 r^4 s^2 (x_n - y_m) / contact_distance^2
+ *         (no singularity), and k = contacts_weight ((C - contacts_max)_+ - (contacts_min - C)_+),
+ *         grad[b,n] = (1/var) [ clash_weight sum_m (clash_distance - d_nm)_+ (x_n - y_m) / d_nm
+ *                               + 6 / contact_distance^2 ( k sum_m r^4 s^2 (x_n - y_m)
+ *                                                          - hotspot_weight sum_h (hotspot_contacts - c_h)_+ r^4 s^2 (x_n - y_hotspot[h]) ) ]
+ * The unit vector of a clash pair is 0 where d is exactly 0 in float32, so every output is finite for finite inputs (coordinates
+ * whose differences square to a finite float).  A weight of 0 switches its term off, energy and force.  `var` is one float in device
+ * memory; the likelihood is left unnormalised.  The caller validates the hotspot list; an index is clamped into 0..M-1 all the same,
+ * since it indexes LDS.  report_out[b] holds GENIE_BINDER_REPORT floats:
+ *   contacts (C), n_contacts (pairs with d < contact_distance), n_interface (design residues with some target residue closer than
+ *   contact_distance), target_min_distance (the smallest d_nm), n_target_clash (pairs with d < clash_distance),
+ *   n_hotspots_contacted (hotspots with some design residue closer than contact_distance), e_target_clash, e_contact, e_hotspot
+ *   (the weighted E above, before the division by 2 var)
+ * (counts are stored as floats: exact up to 2^24; the names differ from the shape report's, so that a merged report keeps both).
+ * hotspot_out [B,H], optional, receives the c_h.  logp_out and grad_out are given together or both NULL; report_out and hotspot_out
+ * may be given alone; at least one output is asked for.
+ * Two launches on `stream`: grid (ceil(N / 64), B), 256 threads; every work-group stages the target in dynamic LDS (12 M + 11 264
+ * bytes; above 64 KiB the kernel's limit is raised) and takes 64 design residues, one per lane; each wave walks a contiguous quarter
+ * of the target in partial sums of 64, the four wave sums are added in wave order, the c_h are reduced over the tile's lanes by
+ * butterfly, and each residue's unscaled clash and contact force, the tile's 8 partial values and its 2 H hotspot values go to `work`
+ * (genie_binder_potential_work_bytes(B, N, H) = 4 B (6 N + (8 + 2 H) ceil(N / 64)) bytes, 4-byte aligned).  The same grid with 64
+ * threads then adds the tiles in tile order, forms the three hinge coefficients -- C and the c_h are global to the particle -- and
+ * writes logp, the report, hotspot_out and the gradient, each residue adding its at most 64 hotspot pairs.  With clash_weight and
+ * contacts_weight 0 and no report asked for the pair walk is skipped.  No allocation, no synchronisation, no host read, no atomics, no
+ * scatter: every output is written once in a fixed order, so two calls on the same inputs are bitwise equal.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 1; M < 1; x0, target or var NULL; H outside 0..GENIE_BINDER_MAX_HOTSPOTS; H > 0 with a NULL hotspot; hotspot_out with
+ * H = 0; a negative or non-finite distance, weight or count (contacts_max alone may be +inf); contacts_max below contacts_min; a
+ * contact_distance of 0; no output asked for; logp_out and grad_out not given together; `work` NULL, misaligned or work_bytes too
+ * small; an M whose staging does not fit in LDS (160 KiB: M above 12 714). */
+#define GENIE_BINDER_REPORT 9   /* contacts, n_contacts, n_interface, target_min_distance, n_target_clash, n_hotspots_contacted,
+                                   e_target_clash, e_contact, e_hotspot */
+#define GENIE_BINDER_MAX_HOTSPOTS 64
+int genie_binder_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int M, const float* target /*[M,3], device*/,
+                           int H, const int32_t* hotspot /*[H] device, ascending; NULL with H = 0*/,
+                           float clash_distance, float clash_weight, float contact_distance, float contacts_min, float contacts_max,
+                           float contacts_weight, float hotspot_contacts, float hotspot_weight, const float* var /*[1], device*/,
+                           float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                           float* report_out /*[B,GENIE_BINDER_REPORT] or NULL*/, float* hotspot_out /*[B,H] or NULL*/,
+                           void* work, size_t work_bytes);
+size_t genie_binder_potential_work_bytes(int B, int N, int H);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
