@@ -123,6 +123,7 @@ SYMBOLS = {
     'genie_binder_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 8 +
                                [C.c_void_p] * 6 + [C.c_size_t]),
     'genie_binder_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'genie_pairwise_tm': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -148,6 +149,8 @@ BINDER_REPORT = ('contacts', 'n_contacts', 'n_interface', 'target_min_distance',
                  'e_contact', 'e_hotspot')      # GENIE_BINDER_REPORT slots
 BINDER_COUNTS = ('n_contacts', 'n_interface', 'n_target_clash', 'n_hotspots_contacted')
 BINDER_MAX_HOTSPOTS = 64        # GENIE_BINDER_MAX_HOTSPOTS
+
+TM_SEEDS, TM_MIN_LENGTH, TM_MAX_LENGTH, TM_MAX_ITER = 11, 4, 1706, 32      # GENIE_TM_SEEDS, _MIN_LENGTH, _MAX_LENGTH, _MAX_ITER
 
 _lib = None
 

@@ -514,6 +514,39 @@ int genie_binder_potential(genie_stream_t stream, int B, int N, const float* x0 
                            void* work, size_t work_bytes);
 size_t genie_binder_potential_work_bytes(int B, int N, int H);
 
+/* The TM-score of every pair of a set of M designs, without a handle (csrc/similarity_kernels.hip): what a diversity count of a
+ * sampler's output is made of.  The score is the project's own and is stated here exactly; it is not a port of the TMscore or TMalign
+ * programs and is a lower bound of theirs (gapless alignments only).  The reference has no counterpart.
+ * x holds C-alpha coordinates in Angstrom, [M,N,3], design m using rows 0..length[m]-1 (the rest is never read); length is a device
+ * int32 array with 4 <= length[m] <= N, validated by the caller (the kernel clamps it into 4..N all the same: it indexes memory).
+ * One pair: the moving chain a has La residues, the fixed chain b has Lb, La <= Lb (equal lengths: the design with the lower index
+ * moves).  At offset o in 0..Lb-La residue a_n corresponds to b_{o+n}.  Lnorm = La (norm 0, 'shorter') or Lb (norm 1, 'longer');
+ *   d0(L) = max(0.5, 1.24 (L - 15)^(1/3) - 1.8) for L > 15, else 0.5;  d0 = d0(Lnorm).
+ * Seeds: GENIE_TM_SEEDS = 11 windows over a's indices, in this order: (0, La); then for level k = 1, 2 the n_k = 2^(k+1) - 1 windows of
+ * length len_k = max(ceil(La / 2^k), 4) that start at floor(j (La - len_k) / (n_k - 1)), j = 0..n_k-1.
+ * Ascent from a seed, n_iter iterations: iteration 0 has weights w_n = 1 inside the window, 0 outside; every iteration takes the weighted
+ * centroids c_p, c_q, the proper rotation R of Horn's quaternion of sum_n w_n (a_n - c_p)(b_{o+n} - c_q)^T (a mirror image does not fit),
+ *   d_n^2 = |R (a_n - c_p) - (b_{o+n} - c_q)|^2 for all La residues,   score = (1 / Lnorm) sum_n 1 / (1 + d_n^2 / d0^2),
+ * and hands w_n = (1 / (1 + d_n^2 / d0^2))^2 to the next one (the majorise-minimise step of the TM objective: in exact arithmetic the
+ * score never decreases).  A seed's value is the largest score of its iterations, tm(a, b, o) the largest over the seeds, tm(a, b) the
+ * largest over the offsets, ties to the lowest offset, then the lowest seed.
+ *   tm[i,j] = tm[j,i] = tm(a, b);  offset[i,j] = offset[j,i] = the winning offset in the longer chain;
+ *   rmsd[i,j] = rmsd[j,i] = sqrt(mean_n d_n^2) of seed 0, iteration 0 at the winning offset: the plain fit of all aligned residues.
+ * The diagonal is written as tm 1, rmsd 0, offset 0 without being computed.
+ * One launch on `stream`: grid (M, M), 256 threads, 28 N + 96 bytes of dynamic LDS; the work-groups below the diagonal return at once,
+ * the one of pair i < j stages both chains in LDS, each centred on its own centroid, deals the (offset, seed) items to its four waves
+ * in a fixed order, sums inside a wave by butterfly and writes both [i,j] and [j,i].  No allocation, no synchronisation, no host read,
+ * no atomics, no work buffer: two calls on the same inputs are bitwise equal and the three matrices are exactly symmetric.
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error(NULL) naming this entry and the argument: M outside
+ * 1..65535; N outside GENIE_TM_MIN_LENGTH..GENIE_TM_MAX_LENGTH; n_iter outside 1..GENIE_TM_MAX_ITER; a norm other than 0 or 1; a NULL
+ * pointer. */
+#define GENIE_TM_SEEDS 11
+#define GENIE_TM_MIN_LENGTH 4
+#define GENIE_TM_MAX_LENGTH 1706    /* the longest chain the samplers take */
+#define GENIE_TM_MAX_ITER 32
+int genie_pairwise_tm(genie_stream_t stream, int M, int N, const float* x /*[M,N,3]*/, const int* length /*[M], 4..N, device*/,
+                      int norm /*0 shorter, 1 longer*/, int n_iter, float* tm /*[M,M]*/, float* rmsd /*[M,M]*/, int* offset /*[M,M]*/);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
