@@ -1,0 +1,3 @@
+"""Not in the reference: fold guidance towards a template backbone or away from known ones by TM-score, the differentiable
+FoldPotential (genie2_amd/smc.py, csrc/fold_kernels.hip), beside the binder guidance of genie/sampler/binder.py."""
+from genie2_amd.smc import FoldPotential, check_fold_bounds  # noqa: F401

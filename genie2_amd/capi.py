@@ -124,6 +124,9 @@ SYMBOLS = {
                                [C.c_void_p] * 6 + [C.c_size_t]),
     'genie_binder_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'genie_pairwise_tm': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'genie_fold_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                             [C.c_size_t]),
+    'genie_fold_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -151,6 +154,10 @@ BINDER_COUNTS = ('n_contacts', 'n_interface', 'n_target_clash', 'n_hotspots_cont
 BINDER_MAX_HOTSPOTS = 64        # GENIE_BINDER_MAX_HOTSPOTS
 
 TM_SEEDS, TM_MIN_LENGTH, TM_MAX_LENGTH, TM_MAX_ITER = 11, 4, 1706, 32      # GENIE_TM_SEEDS, _MIN_LENGTH, _MAX_LENGTH, _MAX_ITER
+
+FOLD_REPORT = ('tm_nearest', 'nearest', 'tm_lowest_wanted', 'n_fold_violations', 'e_fold')      # GENIE_FOLD_REPORT slots
+FOLD_COUNTS = ('nearest', 'n_fold_violations')
+FOLD_MAX_REFERENCES = 4096      # GENIE_FOLD_MAX_REFERENCES
 
 _lib = None
 

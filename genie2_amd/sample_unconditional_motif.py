@@ -46,13 +46,18 @@ writes outdir/sheet/{length}_{index}.txt as that CLI does, and lengths that cann
 `--contacts_max`, `--contacts_weight`, `--target_clash_distance`, `--target_clash_weight`, `--target_standoff`, `--binder_tausq`,
 `--write_binder` and `--write_complex`: the flags of add_binder_arguments in the same module) adds binder guidance against a fixed
 target, summed after all the others; `--write_binder` writes outdir/binder/{length}_{index}.txt and `--write_complex`
-outdir/complex/{length}_{index}.pdb as that CLI does."""
+outdir/complex/{length}_{index}.pdb as that CLI does.
+
+`--template_pdb` and `--avoid_dir` (with `--template_tm_min`, `--template_weight`, `--avoid_tm_max`, `--avoid_weight`,
+`--avoid_representatives`, `--fold_iterations`, `--fold_tausq` and `--write_fold`: the flags of add_fold_arguments in the same module)
+add fold guidance towards a template backbone or away from known ones, summed after all the others; `--write_fold` writes
+outdir/fold/{length}_{index}.txt as that CLI does, and lengths without a reference of their own length are skipped."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_guidance_arguments, add_secstruct_arguments,
-                                         add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
+from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_fold_arguments, add_guidance_arguments,
+                                         add_secstruct_arguments, add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
 
 
 def load_motif_segments(filepath):
@@ -150,6 +155,7 @@ def build_parser():
     add_sheet_arguments(p)
     add_symmetry_arguments(p)
     add_binder_arguments(p)
+    add_fold_arguments(p)
     return p
 
 

@@ -2,7 +2,7 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure, sheet, symmetry or binder term (below), is needed.
+least one of the three, or a secondary-structure, sheet, symmetry, binder or fold term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -51,9 +51,23 @@ placement kept (the files under pdbs/ are centred per design); residue numbers r
 `--target_pdb` ends the run.  Not built: rotating the target, per-design-residue interface masks, all-atom or side-chain terms, and
 feeding the target to the denoiser.
 
+`--template_pdb FILE` guides every design towards the fold of a backbone: a FoldPotential (csrc/fold_kernels.hip) keeps the design's
+TM-score to the file's C-alpha atoms (the project's gapless score of genie2_amd/similarity.py, the design moving) at or above
+`--template_tm_min` (default 0.6; weight `--template_weight`).  `--avoid_dir DIR` guides every design away from known folds: its
+TM-score to every backbone of DIR/pdbs/*.pdb (or DIR/*.pdb) is kept at or below `--avoid_tm_max` (default 0.5; weight
+`--avoid_weight` each); `--avoid_representatives` keeps of them the designs that DIR/diversity/clusters.txt (python -m
+genie2_amd.cluster_designs) names as representatives, and ends the run where that file is missing.  Both may be given; the term is
+summed after everything else and enough on its own.  A reference counts for designs of exactly its own length: a template of another
+length skips the length, avoided backbones of other lengths are ignored there, and a length left without a reference is skipped;
+more than 4096 references of one length end the run.  `--fold_iterations` (default 16) are the ascent steps per seed,
+`--fold_tausq` the likelihood variance.  `--write_fold` adds outdir/fold/{length}_{index}.txt: a line `ref NAME TM LO HI` per
+reference (the written design's TM-score to it and the range asked for), then one `key value` line per field of
+FoldPotential.describe.  Not built: references of another length or with gaps, per-residue masks on a reference, a
+best-of-several-templates form, coupling between the particles of a batch.
+
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
-add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments and add_binder_arguments too and then guides
+add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments, add_binder_arguments and add_fold_arguments too and then guides
 with the sum of the potentials asked for."""
 import os
 
@@ -476,6 +490,157 @@ def write_complex(positions, target, directory, length, offset):
         F.save_np_features_to_pdb(f, os.path.join(directory, '{}_{}.pdb'.format(length, offset + i)))
 
 
+FOLD_DEFAULTS = dict(template_pdb=None, template_tm_min=0.6, template_weight=1.0, avoid_dir=None, avoid_tm_max=0.5, avoid_weight=1.0,
+                     avoid_representatives=False, fold_iterations=16, fold_tausq=1.0, write_fold=False)
+FOLD_MAX_REFERENCES = 4096      # capi.FOLD_MAX_REFERENCES: the most references of one length
+
+
+def add_fold_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    parser.add_argument('--template_pdb', type=str, default=None,
+                        help='Guide every design to a TM-score of at least --template_tm_min to the C-alpha backbone of this file (same '
+                             'length as the design); default: no such term' + tail)
+    parser.add_argument('--template_tm_min', type=float, default=0.6, help='TM-score to the template to stay at or above' + tail)
+    parser.add_argument('--template_weight', type=float, default=1.0, help='Weight of the template term' + tail)
+    parser.add_argument('--avoid_dir', type=str, default=None,
+                        help='Guide every design to a TM-score of at most --avoid_tm_max to every backbone of its own length in this '
+                             'folder (its pdbs/*.pdb, else its *.pdb); default: no such term' + tail)
+    parser.add_argument('--avoid_tm_max', type=float, default=0.5, help='TM-score to every avoided backbone to stay at or below' + tail)
+    parser.add_argument('--avoid_weight', type=float, default=1.0, help='Weight of every avoided backbone' + tail)
+    parser.add_argument('--avoid_representatives', action='store_true',
+                        help='Of --avoid_dir keep the cluster representatives that its diversity/clusters.txt names '
+                             '(genie2_amd.cluster_designs writes it)' + tail)
+    parser.add_argument('--fold_iterations', type=int, default=16, help='Ascent iterations per seed of the TM-score, 1..32' + tail)
+    parser.add_argument('--fold_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the fold terms, Angstrom^2' + tail)
+    parser.add_argument('--write_fold', action='store_true',
+                        help='Write outdir/fold/{length}_{index}.txt: the TM-score of every written structure to every reference, the '
+                             'nearest reference, the violated bounds and the energy' + tail)
+
+
+def cluster_representatives(path):
+    """The names in the `representative` column of a clusters.txt of genie2_amd.cluster_designs, in file order, each once."""
+    out = []
+    with open(path) as fh:
+        for line in fh:
+            fields = line.split()
+            if fields and not fields[0].startswith('#') and len(fields) >= 4 and fields[3] not in out:
+                out.append(fields[3])
+    return out
+
+
+def fold_constants(params):
+    """The fold keys of a runner's constants: the flags of add_fold_arguments; with --template_pdb or --avoid_dir also 'fold', the
+    references read and ready to travel to a worker process: a list of dicts 'name', 'xyz' (float32 numpy [L, 3]), 'lo', 'hi',
+    'weight', 'template' (bool), the template first, then the avoided backbones in file-name order.  A fold flag without either, a
+    value out of range, a file or folder that does not hold up and --avoid_representatives without a clusters.txt end the run here."""
+    import math
+    from .cluster_designs import design_files
+    from .similarity import load_designs
+    c = {k: params.get(k, v) for k, v in FOLD_DEFAULTS.items()}
+    c['avoid_representatives'], c['write_fold'] = bool(c['avoid_representatives']), bool(c['write_fold'])
+    c['fold'] = None
+    if c['template_pdb'] is None and c['avoid_dir'] is None:
+        given = [k for k, v in FOLD_DEFAULTS.items() if c[k] != v]
+        if given:
+            raise SystemExit('%s: a fold flag needs --template_pdb or --avoid_dir, the backbones it is about' % ', '.join('--' + k for k in given))
+        return c
+    if c['avoid_representatives'] and c['avoid_dir'] is None:
+        raise SystemExit('--avoid_representatives needs --avoid_dir, the folder whose clusters it reads')
+    if not (0.0 < c['template_tm_min'] <= 1.0):
+        raise SystemExit('--template_tm_min must be above 0 and at most 1, got %r' % (c['template_tm_min'],))
+    if not (0.0 <= c['avoid_tm_max'] < 1.0):
+        raise SystemExit('--avoid_tm_max must be at least 0 and below 1, got %r' % (c['avoid_tm_max'],))
+    for k in ('template_weight', 'avoid_weight'):
+        if not (math.isfinite(c[k]) and c[k] >= 0):
+            raise SystemExit('--%s must be finite and >= 0, got %r' % (k, c[k]))
+    if not 1 <= c['fold_iterations'] <= 32:
+        raise SystemExit('--fold_iterations must be in 1..32, got %r' % (c['fold_iterations'],))
+    if not (math.isfinite(c['fold_tausq']) and c['fold_tausq'] > 0):
+        raise SystemExit('--fold_tausq must be finite and > 0, got %r' % (c['fold_tausq'],))
+    refs = []
+
+    def read(files, lo, hi, weight, template):
+        try:
+            x, lengths, names = load_designs(files)
+        except (OSError, ValueError) as e:
+            raise SystemExit('--template_pdb / --avoid_dir: %s' % e) from None
+        for m, name in enumerate(names):
+            refs.append(dict(name=name, xyz=x[m, :lengths[m]].numpy().copy(), lo=float(lo), hi=float(hi), weight=float(weight), template=template))
+
+    if c['template_pdb'] is not None:
+        read([c['template_pdb']], c['template_tm_min'], math.inf, c['template_weight'], True)
+    if c['avoid_dir'] is not None:
+        files = design_files(c['avoid_dir'])
+        if c['avoid_representatives']:
+            table = os.path.join(c['avoid_dir'], 'diversity', 'clusters.txt')
+            if not os.path.isfile(table):
+                raise SystemExit('--avoid_representatives needs %s: run python -m genie2_amd.cluster_designs --indir %s first'
+                                 % (table, c['avoid_dir']))
+            keep = set(cluster_representatives(table))
+            files = [f for f in files if os.path.basename(f)[:-4] in keep]
+            if not files:
+                raise SystemExit('%s names no design of %s' % (table, c['avoid_dir']))
+        read(files, 0.0, c['avoid_tm_max'], c['avoid_weight'], False)
+    if not any(r['weight'] > 0 for r in refs):
+        raise SystemExit('--template_weight / --avoid_weight: every fold reference has weight 0')
+    c['fold'] = refs
+    return c
+
+
+def has_fold_terms(constants):
+    return constants.get('fold') is not None
+
+
+def fold_references(constants, length):
+    """The fold references that apply at this length: those of exactly `length` residues -- none at all where the template is of
+    another length (a template of another length skips the length, as a blueprint does) or every one left has weight 0."""
+    refs = constants.get('fold') or []
+    if any(r['template'] and len(r['xyz']) != length for r in refs):
+        return []
+    refs = [r for r in refs if len(r['xyz']) == length]
+    return refs if any(r['weight'] > 0 for r in refs) else []
+
+
+def fold_lengths(tasks, constants):
+    """The tasks whose length has a fold reference (fold_references); the others are skipped with one printed line.  More than
+    FOLD_MAX_REFERENCES references of one length end the run."""
+    if not has_fold_terms(constants):
+        return tasks
+    count = {t['length']: len(fold_references(constants, t['length'])) for t in tasks}
+    for length, n in count.items():
+        if n > FOLD_MAX_REFERENCES:
+            raise SystemExit('%d fold references of %d residues: at most %d of one length (--avoid_representatives keeps one per cluster)'
+                             % (n, length, FOLD_MAX_REFERENCES))
+    other = [t['length'] for t in tasks if not count[t['length']]]
+    if other:
+        print('skipping lengths without a fold reference of their own length: {}'.format(', '.join(map(str, other))))
+    return [t for t in tasks if count[t['length']]]
+
+
+def fold_potential(constants, length, abar, device):
+    """The FoldPotential the constants ask for at this length (its references' names as `.names`), or None when they name no
+    reference.  (Lengths without a reference never get here: fold_lengths drops them when the tasks are made.)"""
+    if not has_fold_terms(constants):
+        return None
+    import numpy as np
+    from .smc import FoldPotential
+    refs = fold_references(constants, length)
+    pot = FoldPotential(length, abar, np.stack([r['xyz'] for r in refs]), [(r['lo'], r['hi'], r['weight']) for r in refs],
+                        n_iter=constants['fold_iterations'], tausq=constants['fold_tausq'], device=device)
+    pot.names, pot.ranges = [r['name'] for r in refs], [(r['lo'], r['hi']) for r in refs]
+    return pot
+
+
+def write_fold_report(tm, names, ranges, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a line `ref <name> <tm %.3f> <lo> <hi>` per reference (`names`,
+    `ranges`, and row i of `tm` [rows, R], FoldPotential.tm_of of TwistedSampler.last_positions), then a `key value` line per field
+    of `report` (the fold fields of last_shape), %.3f for TM-scores and the energy, %d for counts."""
+    from .capi import FOLD_COUNTS
+    rows = tm.tolist()
+    write_report(report, FOLD_COUNTS, directory, length, offset,
+                 ['\n'.join('ref {} {:.3f} {:g} {:g}'.format(n, v, lo, hi) for n, v, (lo, hi) in zip(names, row, ranges)) for row in rows])
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -520,13 +685,14 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, symmetry and binder potentials the
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, symmetry, binder and fold potentials the
     constants ask for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
 
     def guided_lengths(self, tasks, params):
-        """The tasks whose length the restraints, the blueprint, the ladder and the symmetric layout allow."""
+        """The tasks whose length the restraints, the blueprint, the ladder, the symmetric layout and the fold references allow."""
         tasks = target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
-        return symmetric_lengths(ladder_lengths(tasks, sheet_constants(params)['ladder']), symmetry_constants(params))
+        tasks = symmetric_lengths(ladder_lengths(tasks, sheet_constants(params)['ladder']), symmetry_constants(params))
+        return fold_lengths(tasks, fold_constants(params))
 
     def create_tasks(self, params):
         return self.guided_lengths(super().create_tasks(params), params)
@@ -540,6 +706,7 @@ class GuidedRunner(UnconditionalRunner):
         c.update(sheet_constants(params))
         c.update(symmetry_constants(params))
         c.update(binder_constants(params))
+        c.update(fold_constants(params))
         return c
 
     def batch_potentials(self, constants, length, abar, device):
@@ -563,13 +730,14 @@ class GuidedRunner(UnconditionalRunner):
             sheet = sheet_potential(constants, length, abar, device)
             symmetry = symmetry_potential(constants, length, abar, device)
             binder = binder_potential(constants, length, abar, device)
+            fold = fold_potential(constants, length, abar, device)
             chains = {'chain_lengths': symmetry.chain_lengths()} if constants['unit_chains'] else {}
             for batch, offset in self.batches(constants, outdir, length):
                 sampler.sample({
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
                     'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet,
-                                                        symmetry, binder),
+                                                        symmetry, binder, fold),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **chains, **self.partial_params(constants)})
@@ -594,16 +762,21 @@ class GuidedRunner(UnconditionalRunner):
                                         os.path.join(outdir, 'binder'), length, offset)
                 if constants['write_complex'] and binder is not None:
                     write_complex(sampler.last_positions.numpy(), constants['target'], os.path.join(outdir, 'complex'), length, offset)
+                if constants['write_fold'] and fold is not None:
+                    write_fold_report(fold.tm_of(sampler.last_positions.to(fold.device)).cpu(), fold.names, fold.ranges,
+                                      report_fields(sampler.last_shape, capi.FOLD_REPORT), os.path.join(outdir, 'fold'), length, offset)
 
 
 class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
-        if not (has_shape_terms(c) or has_secstruct_terms(c) or has_sheet_terms(c) or has_symmetry_terms(c) or has_binder_terms(c)):
+        if not (has_shape_terms(c) or has_secstruct_terms(c) or has_sheet_terms(c) or has_symmetry_terms(c) or has_binder_terms(c)
+                or has_fold_terms(c)):
             raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
                              'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target), a sheet term '
                              '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file), a binder term (--target_pdb '
-                             'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance) or --symmetry')
+                             'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance), a fold term (--template_pdb, --avoid_dir) '
+                             'or --symmetry')
         return c
 
 
@@ -616,6 +789,7 @@ def build_parser():
     add_sheet_arguments(p)
     add_symmetry_arguments(p)
     add_binder_arguments(p)
+    add_fold_arguments(p)
     return p
 
 

@@ -9,7 +9,8 @@ TMalign programs, and a lower bound of theirs.
     summary = diversity_summary(out['tm'], labels)
 
 Not here: alignments with internal gaps (TM-align's dynamic programming), so designs of different lengths that differ by insertions
-score lower than they would there; a query-versus-reference (novelty) form; designability; any use of the score while sampling."""
+score lower than they would there; a query-versus-reference (novelty) form; designability.  (The score inside the sampling loop
+is smc.FoldPotential, csrc/fold_kernels.hip.)"""
 import math
 import numbers
 

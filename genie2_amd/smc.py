@@ -1468,6 +1468,94 @@ class BinderPotential(_HipPotential):
         return tuple(t for t in outs if t is not None)
 
 
+def check_fold_bounds(bounds, n_refs):
+    """Per-reference rows (lo, hi, weight) -- or (lo, hi): weight 1 -- as a float64 tensor [n_refs, 3]: TM-scores to stay between,
+    0 <= lo <= hi, lo finite, hi possibly inf, weight finite and >= 0; a ValueError otherwise."""
+    import math
+    try:
+        rows = [[float(v) for v in row] for row in (bounds.tolist() if torch.is_tensor(bounds) else bounds)]
+    except (TypeError, ValueError):
+        raise ValueError('bounds must hold one (lo, hi[, weight]) row per reference, got %r' % (bounds,)) from None
+    if len(rows) != n_refs or any(len(row) not in (2, 3) for row in rows):
+        raise ValueError('bounds must hold one (lo, hi[, weight]) row per reference: %d rows for %d references' % (len(rows), n_refs))
+    rows = [row + [1.0] if len(row) == 2 else row for row in rows]
+    for r, (lo, hi, weight) in enumerate(rows):
+        if not (math.isfinite(lo) and lo >= 0 and hi >= lo):
+            raise ValueError('bounds of reference %d must be (lo, hi) with 0 <= lo <= hi, lo finite, got (%r, %r)' % (r, lo, hi))
+        if not (math.isfinite(weight) and weight >= 0):
+            raise ValueError('weight of reference %d must be finite and >= 0, got %r' % (r, weight))
+    return torch.tensor(rows, dtype=torch.float64).reshape(n_refs, 3)
+
+
+class FoldPotential(_HipPotential):
+    """Fold guidance as one HIP entry (genie_fold_potential, csrc/fold_kernels.hip; include/genie_hip.h states the mathematics):
+    `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside the other
+    built-in potentials (SumPotential adds them).  It is the score of similarity.PairwiseTM used while sampling: `references` [R, N, 3]
+    are fixed C-alpha backbones of the design's own length, and `bounds` one row (lo, hi[, weight]) per reference, the range its
+    TM-score to every particle is kept in -- (0.6, inf) samples around a template, (0, 0.5) stays away from a known fold.  With n_r the
+    soft number of superposed residues of the seeded ascent (`n_iter` iterations per seed, the particle moving, gapless, offset 0),
+      E = sum_r weight_r [ max(0, N lo_r - n_r)^2 + max(0, n_r - N hi_r)^2 ],   log p = -E / (2 var),
+    var = xstart_variance(alphas_cumprod[step], tausq) computed on the device, so nothing on the per-step path reads device memory
+    from the host.  The gradient is taken with every pair's winning rigid transform held fixed (the envelope theorem makes it the
+    total derivative at a converged ascent); the forward keeps the gradient the kernel computes and the backward scales it.
+
+    Everything is validated on the host before the device is looked at; a potential whose weights are all 0 is a ValueError.  The
+    references and bounds are uploaded once.  `describe(x)` reports every sample of x with the names of capi.FOLD_REPORT:
+    'tm_nearest' (the largest TM to a reference), 'nearest' (its index, int64), 'tm_lowest_wanted' (the smallest TM to a reference
+    with lo > 0; 0 without one), 'n_fold_violations' (references outside their range, int64), 'e_fold' (E): [B] tensors on the
+    potential's device.  `tm_of(x)` is [B, R], every TM-score.
+
+    The defaults (tausq = 1 A^2, weights 1) are design choices: no trained checkpoint is in the tree, so their effect on sample
+    quality is unmeasured.  Not built: references of another length or with gaps, per-residue masks on a reference, a
+    best-of-several-templates form, coupling between the particles of a batch."""
+
+    def __init__(self, n_res, alphas_cumprod, references, bounds, n_iter=16, tausq=1.0, device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or not capi.TM_MIN_LENGTH <= n_res <= capi.TM_MAX_LENGTH:
+            raise ValueError('n_res must be an integer in %d..%d, got %r' % (capi.TM_MIN_LENGTH, capi.TM_MAX_LENGTH, n_res))
+        try:
+            y = torch.as_tensor(references).detach().to(dtype=torch.float32, device='cpu')
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('references must be [R, %d, 3] coordinates, got %r' % (n_res, type(references))) from None
+        if y.dim() != 3 or y.shape[1] != n_res or y.shape[2] != 3:
+            raise ValueError('references must be [R, %d, 3], got %s' % (n_res, tuple(y.shape)))
+        if not 1 <= y.shape[0] <= capi.FOLD_MAX_REFERENCES:
+            raise ValueError('references must hold 1..%d backbones, got %d' % (capi.FOLD_MAX_REFERENCES, y.shape[0]))
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError('references has a coordinate that is not finite')
+        table = check_fold_bounds(bounds, int(y.shape[0]))
+        if isinstance(n_iter, bool) or not isinstance(n_iter, numbers.Integral) or not 1 <= n_iter <= capi.TM_MAX_ITER:
+            raise ValueError('n_iter must be an integer in 1..%d, got %r' % (capi.TM_MAX_ITER, n_iter))
+        if not (_is_scalar(tausq) and math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        if not bool((table[:, 2] > 0).any()):
+            raise ValueError('no term enabled: every reference has weight 0')
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.R, self.n_iter = int(y.shape[0]), int(n_iter)
+        self.references = y.contiguous().to(self.device)
+        self.bounds = table.to(torch.float32).contiguous().to(self.device)
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, want='report')               # (the energy does not depend on var)
+        return _decode_report(report, capi.FOLD_REPORT, capi.FOLD_COUNTS)
+
+    def tm_of(self, x):
+        """[B, R] float32 on the potential's device: the TM-score of every sample of x [B,N,3] to every reference."""
+        return self._launch(self._checked(x), self._one, want='tm')[0]
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous): (logp, grad), (report [B, 5],) or (tm_out [B, R],) as `want` says."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        outs = {'logp': lambda: [torch.empty(B, **f32), torch.empty_like(x), None, None],
+                'report': lambda: [None, None, torch.empty(B, len(capi.FOLD_REPORT), **f32), None],
+                'tm': lambda: [None, None, None, torch.empty(B, self.R, **f32)]}[want]()
+        self._call('genie_fold_potential', self._stream(), B, self.n_res, _ptr(x), self.R, _ptr(self.references), _ptr(self.bounds),
+                   self.n_iter, _ptr(var), *(_ptr(t) for t in outs),
+                   *self._workspace(self.lib.genie_fold_potential_work_bytes(B, self.n_res, self.R)))
+        return tuple(t for t in outs if t is not None)
+
+
 class SumPotential:
     """The sum of twisting functions: `SumPotential(a, b, ...)(x0, step) = a(x0, step) + b(x0, step) + ...`, added in that order.
     `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential); `describe` is the merge of the reports

@@ -547,6 +547,54 @@ size_t genie_binder_potential_work_bytes(int B, int N, int H);
 int genie_pairwise_tm(genie_stream_t stream, int M, int N, const float* x /*[M,N,3]*/, const int* length /*[M], 4..N, device*/,
                       int norm /*0 shorter, 1 longer*/, int n_iter, float* tm /*[M,M]*/, float* rmsd /*[M,M]*/, int* offset /*[M,M]*/);
 
+/* The fold potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle
+ * (csrc/fold_kernels.hip): the score of genie_pairwise_tm between every particle and every one of R fixed reference backbones, kept
+ * in a range per reference -- at or above a minimum for a template whose fold is wanted, at or below a maximum for folds to stay away
+ * from.  It is the use of that score inside the sampling loop.  The reference has no counterpart.
+ * Particles x0 [B,N,3], GENIE_TM_MIN_LENGTH <= N <= GENIE_TM_MAX_LENGTH; references ref [R,N,3], 1 <= R <= GENIE_FOLD_MAX_REFERENCES,
+ * C-alpha coordinates in Angstrom of the same length N, fixed, in device memory; bounds [R,3] (device) holds per reference
+ * (lo_r, hi_r, weight_r) with 0 <= lo_r <= hi_r, hi_r possibly +inf, weight_r >= 0, validated by the caller.
+ * Score of a pair (b, r): the particle moves onto the reference under the identity alignment (gapless, offset 0); d0 = d0(N) and the
+ * GENIE_TM_SEEDS windows over 0..N-1 are those of genie_pairwise_tm.  From seed s the ascent runs n_iter iterations exactly as stated
+ * there: iteration 0 has weights 1 inside the window and 0 outside; every iteration takes the weighted centroids c_p, c_q, the proper
+ * rotation R of Horn's quaternion of sum_n w_n (x_n - c_p)(y_n - c_q)^T,
+ *   d_n^2 = |R (x_n - c_p) - (y_n - c_q)|^2 for all N residues,   g_n = 1 / (1 + d_n^2 / d0^2),
+ * and hands w_n = g_n^2 to the next one.  The seed's value is sum_n g_n of its LAST iteration (genie_pairwise_tm takes the largest of
+ * the iterations; the two are equal in exact arithmetic because the ascent is monotone, and the last is taken here so that the fit the
+ * gradient uses is a fixed one, not whichever of several iterations equal to rounding happened to win).
+ *   n_r = the largest value over the seeds, ties to the lowest seed;  (R*, c_p*, c_q*) = that seed's last fit;  tm_r = n_r / N
+ *   E = sum_r weight_r [ max(0, N lo_r - n_r)^2 + max(0, n_r - N hi_r)^2 ]          (hinges on the soft number of superposed residues)
+ *   logp_out[b] = -E / (2 var)
+ *   grad_out[b,n] = d logp[b] / d x_n WITH EVERY PAIR'S WINNING RIGID TRANSFORM HELD FIXED:
+ *         d n_r / d x_n = -(2 / d0^2) g_n^2 R*^T e_n,   e_n = R* (x_n - c_p*) - (y_n - c_q*),
+ *         grad[b,n] = (2 / (var d0^2)) sum_r k_r g_n^2 R*^T e_n,   k_r = weight_r (max(0, n_r - N hi_r) - max(0, N lo_r - n_r)).
+ * At a converged ascent the transform maximises the score, so this partial derivative is the total one (envelope theorem); nothing
+ * differentiates through the iterations.  A reference whose hinges are both inactive, or whose weight is 0, contributes exactly 0 to
+ * logp and to the gradient.  `var` is one float in device memory; the likelihood is left unnormalised.
+ * report_out[b] holds GENIE_FOLD_REPORT floats: tm_nearest (max_r tm_r), nearest (the lowest r that attains it), tm_lowest_wanted
+ * (min of tm_r over the references with lo_r > 0; 0 when there is none), n_fold_violations (references with max(0, N lo_r - n_r) or
+ * max(0, n_r - N hi_r) positive, whatever their weight), e_fold (E, before the division by 2 var); counts are stored as floats.
+ * tm_out [B,R], optional, receives tm_r.  logp_out and grad_out are given together or both NULL; report_out and tm_out may be given
+ * alone; at least one output is asked for.
+ * Two launches on `stream`.  Grid (R, B), 256 threads, 24 N + 344 bytes of dynamic LDS: the work-group of a pair stages both chains,
+ * each centred on its own centroid, its four waves take the seeds w, w + 4, w + 8 with the lanes striding over the residues and
+ * butterfly sums, and thread 0 writes n_r, the seed and the fit to `work` (genie_fold_potential_work_bytes(B, N, R) = 96 B R bytes,
+ * 4-byte aligned) and tm_r to tm_out.  Grid (ceil(N / 256), B), 256 threads, launched when logp_out or report_out is given: one
+ * thread per residue walks the references in index order and adds the energy, the report and, for references with k_r != 0 only,
+ * its residue's share of the gradient under the stored fit.  No allocation, no synchronisation, no host read, no atomics, no scratch:
+ * every output is written once in a fixed order, so two calls on the same inputs are bitwise equal.  Rows are never read out of range.
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error(NULL) naming this entry and the argument: B outside
+ * 1..65535; N outside GENIE_TM_MIN_LENGTH..GENIE_TM_MAX_LENGTH; R outside 1..GENIE_FOLD_MAX_REFERENCES; n_iter outside
+ * 1..GENIE_TM_MAX_ITER; x0, ref, bounds or var NULL; no output asked for; logp_out and grad_out not given together; `work` NULL,
+ * misaligned or work_bytes too small. */
+#define GENIE_FOLD_REPORT 5     /* tm_nearest, nearest, tm_lowest_wanted, n_fold_violations, e_fold */
+#define GENIE_FOLD_MAX_REFERENCES 4096
+int genie_fold_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int R, const float* ref /*[R,N,3], device*/,
+                         const float* bounds /*[R,3] device: lo, hi, weight*/, int n_iter, const float* var /*[1], device*/,
+                         float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                         float* report_out /*[B,GENIE_FOLD_REPORT] or NULL*/, float* tm_out /*[B,R] or NULL*/, void* work, size_t work_bytes);
+size_t genie_fold_potential_work_bytes(int B, int N, int R);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
