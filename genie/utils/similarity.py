@@ -1,2 +1,2 @@
-from genie2_amd.similarity import (PairwiseTM, cluster_leader, cluster_single, diversity_summary, load_designs,  # noqa: F401
-                                   seed_windows, tm_d0)
+from genie2_amd.similarity import (PairwiseTM, TMAlign, align_sets, cluster_leader, cluster_single, diversity_summary,  # noqa: F401
+                                   length_chunks, load_designs, plan_calls, seed_windows, tm_d0)

@@ -127,6 +127,8 @@ SYMBOLS = {
     'genie_fold_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
                              [C.c_size_t]),
     'genie_fold_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'genie_tm_align': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_int, C.c_float] + [C.c_void_p] * 7),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -154,6 +156,7 @@ BINDER_COUNTS = ('n_contacts', 'n_interface', 'n_target_clash', 'n_hotspots_cont
 BINDER_MAX_HOTSPOTS = 64        # GENIE_BINDER_MAX_HOTSPOTS
 
 TM_SEEDS, TM_MIN_LENGTH, TM_MAX_LENGTH, TM_MAX_ITER = 11, 4, 1706, 32      # GENIE_TM_SEEDS, _MIN_LENGTH, _MAX_LENGTH, _MAX_ITER
+TMALIGN_MAX_LENGTH, TMALIGN_MAX_CELLS, TMALIGN_MAX_ROUNDS = 1024, 131072, 16      # GENIE_TMALIGN_MAX_LENGTH, _MAX_CELLS, _MAX_ROUNDS
 
 FOLD_REPORT = ('tm_nearest', 'nearest', 'tm_lowest_wanted', 'n_fold_violations', 'e_fold')      # GENIE_FOLD_REPORT slots
 FOLD_COUNTS = ('nearest', 'n_fold_violations')

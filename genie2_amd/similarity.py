@@ -8,9 +8,13 @@ TMalign programs, and a lower bound of theirs.
     labels, representatives = cluster_single(out['tm'], 0.6)
     summary = diversity_summary(out['tm'], labels)
 
-Not here: alignments with internal gaps (TM-align's dynamic programming), so designs of different lengths that differ by insertions
-score lower than they would there; a query-versus-reference (novelty) form; designability.  (The score inside the sampling loop
-is smc.FoldPotential, csrc/fold_kernels.hip.)"""
+Designs that differ by an inserted loop or a deleted turn, and queries against references of any length (novelty), go through the
+gapped form, one more HIP launch (genie_tm_align, csrc/tmalign_kernels.hip): the gapless search as a seed, then dynamic programming
+under the TM objective, refitted, for every (query, reference) pair.
+
+    out = TMAlign('cuda:0')(xq, lq, xr, lr, norm='query')   # {'tm', 'rmsd', 'n_aligned', 'rounds'}: [M, R] on the device
+
+Not here: designability.  (The score inside the sampling loop is smc.FoldPotential, csrc/fold_kernels.hip.)"""
 import math
 import numbers
 
@@ -97,6 +101,139 @@ class PairwiseTM(_HipEntry):
         self._call('genie_pairwise_tm', self._stream(), M, N, _ptr(x), _ptr(lengths), norm, n_iter, _ptr(out['tm']), _ptr(out['rmsd']),
                    _ptr(out['offset']))
         return out
+
+
+ALIGN_NORMS = ('query', 'reference', 'shorter', 'longer')       # genie_tm_align's norm 0, 1, 2, 3
+
+
+def _chains(x, lengths, what):
+    """A set of chains for TMAlign: (x as a tensor [M, N, 3], lengths as M ints in 4..N), shape, dtype, lengths and finiteness checked
+    where x lives; `what` names the set in the messages."""
+    x = torch.as_tensor(x)
+    if x.dim() != 3 or x.shape[2] != 3 or x.shape[0] < 1:
+        raise ValueError('%s must be [M >= 1, N, 3], got %s' % (what, tuple(x.shape)))
+    M, N = int(x.shape[0]), int(x.shape[1])
+    if N < capi.TM_MIN_LENGTH:
+        raise ValueError('%s: N must be at least %d residues, got %d' % (what, capi.TM_MIN_LENGTH, N))
+    if not x.dtype.is_floating_point:
+        raise ValueError('%s must have a floating dtype, got %s' % (what, x.dtype))
+    try:
+        lengths = _check_lengths(lengths, M, N)
+    except ValueError as e:
+        raise ValueError('%s: %s' % (what, e)) from None
+    if max(lengths) > capi.TMALIGN_MAX_LENGTH:
+        raise ValueError('%s: a chain has %d residues, the gapped alignment takes %d..%d' % (what, max(lengths), capi.TM_MIN_LENGTH,
+                                                                                          capi.TMALIGN_MAX_LENGTH))
+    used = torch.arange(N, device=x.device)[None, :, None] < torch.as_tensor(lengths, device=x.device)[:, None, None]
+    if not bool(torch.isfinite(torch.where(used, x.detach(), torch.zeros((), dtype=x.dtype, device=x.device))).all()):
+        raise ValueError('%s holds a NaN or an infinity inside a chain' % what)
+    return x, lengths
+
+
+class TMAlign(_HipEntry):
+    """genie_tm_align (include/genie_hip.h) on `device`: `TMAlign()(xq [M,Nq,3], lq, xr [R,Nr,3], lr, norm='query', n_iter=16, n_rounds=8,
+    gap_open=-0.6, return_alignment=False)` returns {'tm', 'rmsd' [M,R] float32, 'n_aligned', 'rounds' [M,R] int32} on the device, from one
+    launch on torch's current stream: every query aligned to every reference by the gapless seeded search (stage 0) and up to `n_rounds`
+    rounds of dynamic programming under the TM objective with the gap opening penalty `gap_open` (-10..0), each refitted by `n_iter`
+    ascent steps; the best stage is returned.  `norm` picks the normalising length: 'query', 'reference', 'shorter' or 'longer'.  Query
+    m uses rows 0..lq[m]-1 (None: all Nq), reference r rows 0..lr[r]-1; the padding beyond the longest chain of each set is trimmed
+    before the launch and never read.  With `return_alignment` the dict also holds 'map' [M,R,Nq] int32 (per query residue the matched
+    reference residue, or -1), 'rot' [M,R,3,3] and 'trans' [M,R,3] with rot x_query + trans ~ x_reference.  Chains have 4..1024 residues
+    and the longest query times the longest reference at most 131072 cells.  The inputs may live anywhere; they are checked where they
+    live -- shapes, a floating dtype, finite values, lengths, the cell limit, every scalar: ValueErrors -- before the device is touched.
+    A GPU entry only: a CPU device is a capi.GenieError."""
+
+    def __init__(self, device='cuda'):
+        self._bind(device, 'genie_tm_align')
+
+    def __call__(self, xq, lq, xr, lr, norm='query', n_iter=16, n_rounds=8, gap_open=-0.6, return_alignment=False):
+        xq, lq = _chains(xq, lq, 'xq')
+        xr, lr = _chains(xr, lr, 'xr')
+        Nq, Nr = max(lq), max(lr)
+        if Nq * Nr > capi.TMALIGN_MAX_CELLS:
+            raise ValueError('the longest query (%d) times the longest reference (%d) is above %d cells' % (Nq, Nr, capi.TMALIGN_MAX_CELLS))
+        if norm not in ALIGN_NORMS:
+            raise ValueError('norm must be one of %s, got %r' % (ALIGN_NORMS, norm))
+        if isinstance(n_iter, bool) or not isinstance(n_iter, numbers.Integral) or not 1 <= n_iter <= capi.TM_MAX_ITER:
+            raise ValueError('n_iter must be an integer in 1..%d, got %r' % (capi.TM_MAX_ITER, n_iter))
+        if isinstance(n_rounds, bool) or not isinstance(n_rounds, numbers.Integral) or not 0 <= n_rounds <= capi.TMALIGN_MAX_ROUNDS:
+            raise ValueError('n_rounds must be an integer in 0..%d, got %r' % (capi.TMALIGN_MAX_ROUNDS, n_rounds))
+        if isinstance(gap_open, bool) or not isinstance(gap_open, numbers.Real) or not -10.0 <= gap_open <= 0.0:       # (NaN fails both)
+            raise ValueError('gap_open must be a number in -10..0, got %r' % (gap_open,))
+        if not isinstance(return_alignment, bool):
+            raise ValueError('return_alignment must be a bool, got %r' % (return_alignment,))
+        f32 = torch.float32
+        out = self._launch(xq[:, :Nq].detach().to(self.device, f32).contiguous(), torch.tensor(lq, dtype=torch.int32).to(self.device),
+                           xr[:, :Nr].detach().to(self.device, f32).contiguous(), torch.tensor(lr, dtype=torch.int32).to(self.device),
+                           ALIGN_NORMS.index(norm), int(n_iter), int(n_rounds), float(gap_open), return_alignment)
+        if return_alignment and Nq < xq.shape[1]:                  # map speaks of the caller's Nq
+            pad = torch.full(out['map'].shape[:2] + (xq.shape[1] - Nq,), -1, dtype=torch.int32, device=self.device)
+            out['map'] = torch.cat([out['map'], pad], dim=2)
+        return out
+
+    def _launch(self, xq, lq, xr, lr, norm, n_iter, n_rounds, gap_open, alignment=False):
+        """One call of the C entry on xq [M,Nq,3], xr [R,Nr,3] float32 and lq [M], lr [R] int32, all contiguous on the device."""
+        M, Nq, R, Nr = xq.shape[0], xq.shape[1], xr.shape[0], xr.shape[1]
+        kw = dict(device=self.device)
+        out = {'tm': torch.empty(M, R, dtype=torch.float32, **kw), 'rmsd': torch.empty(M, R, dtype=torch.float32, **kw),
+               'n_aligned': torch.empty(M, R, dtype=torch.int32, **kw), 'rounds': torch.empty(M, R, dtype=torch.int32, **kw)}
+        if alignment:
+            out.update(map=torch.empty(M, R, Nq, dtype=torch.int32, **kw), rot=torch.empty(M, R, 3, 3, dtype=torch.float32, **kw),
+                       trans=torch.empty(M, R, 3, dtype=torch.float32, **kw))
+        self._call('genie_tm_align', self._stream(), M, Nq, _ptr(xq), _ptr(lq), R, Nr, _ptr(xr), _ptr(lr), norm, n_iter, n_rounds, gap_open,
+                   _ptr(out['tm']), _ptr(out['rmsd']), _ptr(out['n_aligned']), _ptr(out['rounds']), _ptr(out.get('map')),
+                   _ptr(out.get('rot')), _ptr(out.get('trans')))
+        return out
+
+
+def length_chunks(lengths, ratio=1.25, slack=16):
+    """Indices into `lengths` sorted by length (ties by index) and cut into runs whose longest member is at most ratio x the shortest
+    + slack: chains that share a call with little padding."""
+    chunks = []
+    for k in sorted(range(len(lengths)), key=lambda k: (lengths[k], k)):
+        if chunks and lengths[k] <= ratio * lengths[chunks[-1][0]] + slack:
+            chunks[-1].append(k)
+        else:
+            chunks.append([k])
+    return chunks
+
+
+def plan_calls(lq, lr, max_cells=None):
+    """How a query-versus-reference run is dealt to calls of TMAlign: (calls, skipped_pairs).  Every call is (query indices, reference
+    indices) with longest query x longest reference inside the cell limit; a pair is skipped exactly when its own Lq x Lr is above the
+    limit, every other pair is in exactly one call.  Queries and references are chunked by length; a chunk pair that does not fit as a
+    whole is dealt one query at a time to the references that fit it."""
+    max_cells = capi.TMALIGN_MAX_CELLS if max_cells is None else max_cells
+    calls, skipped = [], 0
+    r_chunks = length_chunks(lr)
+    for qc in length_chunks(lq):
+        for rc in r_chunks:
+            if max(lq[q] for q in qc) * max(lr[r] for r in rc) <= max_cells:
+                calls.append((qc, rc))
+                continue
+            for q in qc:
+                fit = [r for r in rc if lq[q] * lr[r] <= max_cells]
+                skipped += len(rc) - len(fit)
+                if fit:
+                    calls.append(([q], fit))
+    return calls, skipped
+
+
+def align_sets(entry, xq, lq, xr, lr, **kw):
+    """TMAlign of every query against every reference through plan_calls: ({'tm', 'rmsd' float32, 'n_aligned', 'rounds' int32} as numpy
+    [M, R], scored bool [M, R], skipped_pairs).  Pairs above the cell limit are left at 0 and marked unscored."""
+    xq, xr = torch.as_tensor(xq), torch.as_tensor(xr)
+    M, R = len(lq), len(lr)
+    out = {'tm': np.zeros((M, R), dtype=np.float32), 'rmsd': np.zeros((M, R), dtype=np.float32),
+           'n_aligned': np.zeros((M, R), dtype=np.int32), 'rounds': np.zeros((M, R), dtype=np.int32)}
+    scored = np.zeros((M, R), dtype=bool)
+    calls, skipped = plan_calls(lq, lr)
+    for qc, rc in calls:
+        part = entry(xq[qc], [lq[q] for q in qc], xr[rc], [lr[r] for r in rc], **kw)
+        for k in out:
+            out[k][np.ix_(qc, rc)] = part[k].cpu().numpy()
+        scored[np.ix_(qc, rc)] = True
+    return out, scored, skipped
 
 
 def _matrix(tm):

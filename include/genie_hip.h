@@ -595,6 +595,54 @@ int genie_fold_potential(genie_stream_t stream, int B, int N, const float* x0 /*
                          float* report_out /*[B,GENIE_FOLD_REPORT] or NULL*/, float* tm_out /*[B,R] or NULL*/, void* work, size_t work_bytes);
 size_t genie_fold_potential_work_bytes(int B, int N, int R);
 
+/* Gapped TM alignment of M queries against R references, without a handle (csrc/tmalign_kernels.hip): the novelty of a design set (the
+ * highest score of a design against known structures of any length) and a diversity count that an inserted loop does not throw.  The
+ * score is the project's own and is stated here exactly; it is not a port of the TMalign program.  It is the TM-score of one explicit
+ * alignment under one explicit superposition, so a lower bound of the true TM-score, and a tighter one than genie_pairwise_tm's.  The
+ * reference has no counterpart.
+ * xq [M,Nq,3] and xr [R,Nr,3] hold C-alpha coordinates in Angstrom; query m uses rows 0..lq[m]-1, reference r rows 0..lr[r]-1 (the rest
+ * is never read); lq, lr are device int32 arrays with 4 <= length <= N, validated by the caller (the kernel clamps them into 4..N).
+ * One pair: a = the shorter chain (equal lengths: the query), b = the longer chain, La <= Lb.  Lnorm = Lq, Lr, La, Lb for norm 0 (query),
+ * 1 (reference), 2 (shorter), 3 (longer); d0 = d0(Lnorm) as for genie_pairwise_tm.
+ * Stage 0, the seed, is genie_pairwise_tm's search of a along b: every offset o in 0..Lb-La, the GENIE_TM_SEEDS windows, n_iter
+ * iterations of the weighted Horn ascent, the score (1 / Lnorm) sum_n 1 / (1 + d_n^2 / d0^2) over all La residues.  The winner is the
+ * largest score over (offset, seed, iteration), ties to the lowest offset, then the lowest seed, then the earliest iteration; its
+ * transform T (T x = R (x - c_p) + c_q) is kept and its alignment is the threading a_n <-> b_{o+n}.
+ * Stages 1..n_rounds each start from the transform of the stage before:
+ *   1. S_ij = 1 / (1 + |T a_i - b_j|^2 / d0^2) for i in 1..La, j in 1..Lb.
+ *   2. The table: val(0, .) = val(., 0) = 0 and path(0, .) = path(., 0) = false (leading gaps are free);
+ *        D = val(i-1, j-1) + S_ij,  H = val(i-1, j) + (path(i-1, j) ? gap_open : 0),  V = val(i, j-1) + (path(i, j-1) ? gap_open : 0);
+ *      if D >= H and D >= V the move is diag, path = true, val = D; otherwise path = false, val = max(H, V) and the move is left (j-1)
+ *      if V >= H, else up (i-1).
+ *   3. Trace back from (La, Lb) along the moves until i = 0 or j = 0; every diag step aligns a_i with b_j.
+ *   4. An alignment equal to the previous stage's (stage 0's threading included) stops the run: the stage is counted in `rounds`, not
+ *      fitted.   5. Fewer than 3 aligned pairs stop it too.
+ *   6. Otherwise n_iter iterations of the same ascent over the aligned pairs only: iteration 0 has weights 1, the score is
+ *      (1 / Lnorm) sum_aligned 1 / (1 + d^2 / d0^2), the weights handed on are (1 / (1 + d^2 / d0^2))^2; the stage's value and transform
+ *      are those of its best iteration, ties to the earliest.
+ * The result is the stage with the largest value, ties to the earliest: tm[m,r] its value, rmsd[m,r] = sqrt(mean d^2) over its aligned
+ * pairs under its transform, n_aligned[m,r] their number, rounds[m,r] the number of table fills run (n_rounds = 0: stage 0 alone, which
+ * is genie_pairwise_tm's score with its alignment and transform).  map [M,R,Nq], optional: per query residue the matched reference
+ * residue or -1 (-1 from lq[m] on).  rot [M,R,9] (row-major 3x3) and trans [M,R,3], optional and given together:
+ * rot x_query + trans ~ x_reference, inverted when the reference was the moving chain.
+ * One launch on `stream`: grid (R, M), 256 threads, one work-group per pair, at most 60 KB of dynamic LDS (both chains, T a, three
+ * rolling diagonals of the table, three alignments and the moves of the whole table at 2 bits a cell).  The table is filled as an
+ * anti-diagonal wavefront with S_ij formed on the fly; a row of the table has one owner thread, which stores its moves a whole dword
+ * at a time.  No allocation, no synchronisation, no host read, no atomics, no work buffer, fixed summation trees: two calls on the same
+ * inputs are bitwise equal.
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error(NULL) naming this entry and the argument: M or R outside
+ * 1..65535; Nq or Nr outside GENIE_TM_MIN_LENGTH..GENIE_TMALIGN_MAX_LENGTH; Nq * Nr above GENIE_TMALIGN_MAX_CELLS; norm outside 0..3;
+ * n_iter outside 1..GENIE_TM_MAX_ITER; n_rounds outside 0..GENIE_TMALIGN_MAX_ROUNDS; gap_open not finite, above 0 or below -10; a NULL
+ * required pointer; rot without trans or trans without rot. */
+#define GENIE_TMALIGN_MAX_LENGTH 1024
+#define GENIE_TMALIGN_MAX_CELLS  131072     /* Nq * Nr of one call */
+#define GENIE_TMALIGN_MAX_ROUNDS 16
+int genie_tm_align(genie_stream_t stream, int M, int Nq, const float* xq /*[M,Nq,3]*/, const int* lq /*[M] device*/,
+                   int R, int Nr, const float* xr /*[R,Nr,3]*/, const int* lr /*[R] device*/,
+                   int norm, int n_iter, int n_rounds, float gap_open,
+                   float* tm, float* rmsd, int* n_aligned, int* rounds /*each [M,R]*/,
+                   int* map /*[M,R,Nq] or NULL*/, float* rot /*[M,R,9] or NULL*/, float* trans /*[M,R,3] or NULL*/);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
