@@ -35,18 +35,18 @@ def group_q(x, starts, seg_len, seg_group, target, rigid):
     return torch.stack(out, dim=-1)
 
 
-def grouped_oracle(x0, starts, seg_len, seg_group, target, var, rigid=True, want_grad=True):
+def grouped_oracle(x0, starts, seg_len, seg_group, target, var, rigid=True, want_grad=True, dtype=torch.float64):
     """{'logp' [B], 'grad' [B,N,3] (or None), 'score' [B,P], 'q' [B,P], 'qg' [B,P,G], 'best' [B], 'rmsd' [B], 'group_rmsd' [B,G]} in
-    float64 on the CPU."""
-    x = x0.detach().double().cpu().requires_grad_(want_grad)
-    qg = group_q(x, starts.cpu(), seg_len, seg_group, target.detach().double().cpu(), rigid)
+    float64 on the CPU (`dtype`: the same statements in another precision, the float32 restatement)."""
+    x = x0.detach().to(dtype).cpu().requires_grad_(want_grad)
+    qg = group_q(x, starts.cpu(), seg_len, seg_group, target.detach().to(dtype).cpu(), rigid)
     q = qg.sum(dim=-1)
     score = -q / (2 * float(var))
     logp = torch.logsumexp(score, dim=1) - np.log(score.shape[1])
     grad = torch.autograd.grad(logp.sum(), x)[0] if want_grad else None
     best = score.detach().argmax(dim=1)
     qgb = qg.detach()[torch.arange(len(best)), best]                       # [B, G]
-    mg = torch.bincount(position_groups(seg_len, seg_group)).double()
+    mg = torch.bincount(position_groups(seg_len, seg_group)).to(dtype)
     return {'logp': logp.detach(), 'grad': grad, 'score': score.detach(), 'q': q.detach(), 'qg': qg.detach(), 'best': best,
             'rmsd': torch.sqrt(qgb.sum(dim=1) / float(mg.sum())), 'group_rmsd': torch.sqrt(qgb / mg[None])}
 

@@ -35,10 +35,11 @@ def residual_q(c, tc, detach_rotation=False):
     return (e ** 2).sum(dim=(-1, -2))
 
 
-def rigid_oracle(x0, starts, seg_len, target, var, detach_rotation=False, want_grad=True):
-    """{'logp' [B], 'grad' [B,N,3] (or None), 'score' [B,P], 'q' [B,P], 'best' [B], 'rmsd' [B]} in float64 on the CPU."""
-    x = x0.detach().double().cpu().requires_grad_(want_grad)
-    t = target.detach().double().cpu()
+def rigid_oracle(x0, starts, seg_len, target, var, detach_rotation=False, want_grad=True, dtype=torch.float64):
+    """{'logp' [B], 'grad' [B,N,3] (or None), 'score' [B,P], 'q' [B,P], 'best' [B], 'rmsd' [B]} in float64 on the CPU (`dtype`: the
+    same statements in another precision, the float32 restatement that tells how much a bound may widen)."""
+    x = x0.detach().to(dtype).cpu().requires_grad_(want_grad)
+    t = target.detach().to(dtype).cpu()
     tc = t - t.mean(dim=0, keepdim=True)
     q = residual_q(centred_selection(x, placement_index(starts.cpu(), seg_len)), tc, detach_rotation)
     score = -q / (2 * float(var))
