@@ -129,6 +129,9 @@ SYMBOLS = {
     'genie_fold_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'genie_tm_align': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_int, C.c_float] + [C.c_void_p] * 7),
+    'genie_fold_align_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 12 + [C.c_size_t]),
+    'genie_fold_align_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -161,6 +164,8 @@ TMALIGN_MAX_LENGTH, TMALIGN_MAX_CELLS, TMALIGN_MAX_ROUNDS = 1024, 131072, 16    
 FOLD_REPORT = ('tm_nearest', 'nearest', 'tm_lowest_wanted', 'n_fold_violations', 'e_fold')      # GENIE_FOLD_REPORT slots
 FOLD_COUNTS = ('nearest', 'n_fold_violations')
 FOLD_MAX_REFERENCES = 4096      # GENIE_FOLD_MAX_REFERENCES
+FOLD_ALIGN_MAX_REFERENCES, FOLD_ALIGN_MAX_STRIDE = 1024, 64      # GENIE_FOLD_ALIGN_MAX_REFERENCES, _MAX_STRIDE
+TMALIGN_NORMS = ('query', 'reference', 'shorter', 'longer')      # norm 0..3 of genie_tm_align and genie_fold_align_potential
 
 _lib = None
 

@@ -51,7 +51,9 @@ outdir/complex/{length}_{index}.pdb as that CLI does.
 `--template_pdb` and `--avoid_dir` (with `--template_tm_min`, `--template_weight`, `--avoid_tm_max`, `--avoid_weight`,
 `--avoid_representatives`, `--fold_iterations`, `--fold_tausq` and `--write_fold`: the flags of add_fold_arguments in the same module)
 add fold guidance towards a template backbone or away from known ones, summed after all the others; `--write_fold` writes
-outdir/fold/{length}_{index}.txt as that CLI does, and lengths without a reference of their own length are skipped."""
+outdir/fold/{length}_{index}.txt as that CLI does, and lengths without a reference of their own length are skipped.  `--fold_align
+gapped` (with `--fold_norm`, `--fold_rounds`, `--fold_gap_open`, `--fold_offset_stride`) scores under gapped alignment instead, so
+that references of any length apply, exactly as that CLI describes."""
 import os
 
 from .motif import load_motif_spec

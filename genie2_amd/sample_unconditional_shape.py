@@ -62,8 +62,15 @@ length skips the length, avoided backbones of other lengths are ignored there, a
 more than 4096 references of one length end the run.  `--fold_iterations` (default 16) are the ascent steps per seed,
 `--fold_tausq` the likelihood variance.  `--write_fold` adds outdir/fold/{length}_{index}.txt: a line `ref NAME TM LO HI` per
 reference (the written design's TM-score to it and the range asked for), then one `key value` line per field of
-FoldPotential.describe.  Not built: references of another length or with gaps, per-residue masks on a reference, a
-best-of-several-templates form, coupling between the particles of a batch.
+FoldPotential.describe.  `--fold_align gapped` (default `gapless`: all of the above, unchanged) scores under the gapped alignment of
+genie2_amd.novelty instead, with an AlignedFoldPotential (csrc/fold_align_kernels.hip): every reference of 4..1024 residues applies
+at every design length where length times its own is at most 131072; a template that does not fit a length skips it, avoided
+backbones that do not fit are dropped there with a printed count, and more than 1024 applicable references end the run.
+`--fold_norm query|reference|shorter|longer` (default query, novelty's), `--fold_rounds` (default 8), `--fold_gap_open` (default
+-0.6) and `--fold_offset_stride` (default 1: every offset of the gapless stage) are the alignment's arguments and need
+`--fold_align gapped`; the `ref` lines of `--write_fold` become `ref NAME TM LO HI LENGTH N_ALIGNED`.  Not built: gradients across
+a change of alignment, per-residue masks on a reference, a best-of-several-templates form, coupling between the particles of a
+batch.
 
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
@@ -493,6 +500,10 @@ def write_complex(positions, target, directory, length, offset):
 FOLD_DEFAULTS = dict(template_pdb=None, template_tm_min=0.6, template_weight=1.0, avoid_dir=None, avoid_tm_max=0.5, avoid_weight=1.0,
                      avoid_representatives=False, fold_iterations=16, fold_tausq=1.0, write_fold=False)
 FOLD_MAX_REFERENCES = 4096      # capi.FOLD_MAX_REFERENCES: the most references of one length
+# the flags of --fold_align gapped (kept apart: FOLD_DEFAULTS is what the gapless form takes)
+FOLD_ALIGN_DEFAULTS = dict(fold_align='gapless', fold_norm='query', fold_rounds=8, fold_gap_open=-0.6, fold_offset_stride=1)
+FOLD_ALIGN_MAX_REFERENCES = 1024        # capi.FOLD_ALIGN_MAX_REFERENCES: the most references that apply at one length under gapped alignment
+FOLD_ALIGN_LENGTHS, FOLD_ALIGN_MAX_CELLS = (4, 1024), 131072       # capi.TM_MIN_LENGTH, TMALIGN_MAX_LENGTH, TMALIGN_MAX_CELLS
 
 
 def add_fold_arguments(parser):
@@ -515,6 +526,15 @@ def add_fold_arguments(parser):
     parser.add_argument('--write_fold', action='store_true',
                         help='Write outdir/fold/{length}_{index}.txt: the TM-score of every written structure to every reference, the '
                              'nearest reference, the violated bounds and the energy' + tail)
+    parser.add_argument('--fold_align', type=str, default='gapless', choices=('gapless', 'gapped'),
+                        help='gapless: a reference counts for designs of its own length, under the identity alignment; gapped: every '
+                             'reference of 4..1024 residues counts at every length, under the gapped alignment of genie2_amd.novelty' + tail)
+    parser.add_argument('--fold_norm', type=str, default='query', choices=('query', 'reference', 'shorter', 'longer'),
+                        help='With --fold_align gapped: the length that normalises the TM-score (query: the design)' + tail)
+    parser.add_argument('--fold_rounds', type=int, default=8, help='With --fold_align gapped: rounds of dynamic programming, 0..16' + tail)
+    parser.add_argument('--fold_gap_open', type=float, default=-0.6, help='With --fold_align gapped: gap opening penalty, -10..0' + tail)
+    parser.add_argument('--fold_offset_stride', type=int, default=1,
+                        help='With --fold_align gapped: the gapless stage visits every s-th offset and the last one, 1..64' + tail)
 
 
 def cluster_representatives(path):
@@ -538,9 +558,16 @@ def fold_constants(params):
     from .similarity import load_designs
     c = {k: params.get(k, v) for k, v in FOLD_DEFAULTS.items()}
     c['avoid_representatives'], c['write_fold'] = bool(c['avoid_representatives']), bool(c['write_fold'])
+    c.update({k: params.get(k, v) for k, v in FOLD_ALIGN_DEFAULTS.items()})
     c['fold'] = None
+    if c['fold_align'] not in ('gapless', 'gapped'):
+        raise SystemExit('--fold_align must be gapless or gapped, got %r' % (c['fold_align'],))
+    if c['fold_align'] != 'gapped':
+        given = [k for k, v in FOLD_ALIGN_DEFAULTS.items() if k != 'fold_align' and c[k] != v]
+        if given:
+            raise SystemExit('%s: an alignment flag needs --fold_align gapped' % ', '.join('--' + k for k in given))
     if c['template_pdb'] is None and c['avoid_dir'] is None:
-        given = [k for k, v in FOLD_DEFAULTS.items() if c[k] != v]
+        given = [k for k, v in list(FOLD_DEFAULTS.items()) + list(FOLD_ALIGN_DEFAULTS.items()) if c[k] != v]
         if given:
             raise SystemExit('%s: a fold flag needs --template_pdb or --avoid_dir, the backbones it is about' % ', '.join('--' + k for k in given))
         return c
@@ -557,6 +584,14 @@ def fold_constants(params):
         raise SystemExit('--fold_iterations must be in 1..32, got %r' % (c['fold_iterations'],))
     if not (math.isfinite(c['fold_tausq']) and c['fold_tausq'] > 0):
         raise SystemExit('--fold_tausq must be finite and > 0, got %r' % (c['fold_tausq'],))
+    if c['fold_norm'] not in ('query', 'reference', 'shorter', 'longer'):
+        raise SystemExit('--fold_norm must be query, reference, shorter or longer, got %r' % (c['fold_norm'],))
+    if not 0 <= c['fold_rounds'] <= 16:
+        raise SystemExit('--fold_rounds must be in 0..16, got %r' % (c['fold_rounds'],))
+    if not -10.0 <= c['fold_gap_open'] <= 0.0:
+        raise SystemExit('--fold_gap_open must be in -10..0, got %r' % (c['fold_gap_open'],))
+    if not 1 <= c['fold_offset_stride'] <= 64:
+        raise SystemExit('--fold_offset_stride must be in 1..64, got %r' % (c['fold_offset_stride'],))
     refs = []
 
     def read(files, lo, hi, weight, template):
@@ -591,10 +626,27 @@ def has_fold_terms(constants):
     return constants.get('fold') is not None
 
 
+def fold_gapped(constants):
+    return constants.get('fold_align', 'gapless') == 'gapped'
+
+
+def fold_fits(n_ref, length):
+    """Whether a reference of n_ref residues can be aligned to a design of `length`: both of 4..1024 residues, at most 131072 cells."""
+    lo, hi = FOLD_ALIGN_LENGTHS
+    return lo <= n_ref <= hi and lo <= length <= hi and n_ref * length <= FOLD_ALIGN_MAX_CELLS
+
+
 def fold_references(constants, length):
     """The fold references that apply at this length: those of exactly `length` residues -- none at all where the template is of
-    another length (a template of another length skips the length, as a blueprint does) or every one left has weight 0."""
+    another length (a template of another length skips the length, as a blueprint does) or every one left has weight 0.  With
+    --fold_align gapped: those that fit the length (fold_fits) -- none at all where the template does not or every one left has
+    weight 0."""
     refs = constants.get('fold') or []
+    if fold_gapped(constants):
+        if any(r['template'] and not fold_fits(len(r['xyz']), length) for r in refs):
+            return []
+        refs = [r for r in refs if fold_fits(len(r['xyz']), length)]
+        return refs if any(r['weight'] > 0 for r in refs) else []
     if any(r['template'] and len(r['xyz']) != length for r in refs):
         return []
     refs = [r for r in refs if len(r['xyz']) == length]
@@ -606,6 +658,8 @@ def fold_lengths(tasks, constants):
     FOLD_MAX_REFERENCES references of one length end the run."""
     if not has_fold_terms(constants):
         return tasks
+    if fold_gapped(constants):
+        return fold_lengths_gapped(tasks, constants)
     count = {t['length']: len(fold_references(constants, t['length'])) for t in tasks}
     for length, n in count.items():
         if n > FOLD_MAX_REFERENCES:
@@ -617,28 +671,62 @@ def fold_lengths(tasks, constants):
     return [t for t in tasks if count[t['length']]]
 
 
+def fold_lengths_gapped(tasks, constants):
+    """fold_lengths under --fold_align gapped: a length is skipped where the template does not fit it or nothing with a weight does,
+    with one printed line; avoided backbones that do not fit a kept length are dropped there, with a printed count per length; more
+    than FOLD_ALIGN_MAX_REFERENCES applicable references end the run."""
+    refs = constants.get('fold') or []
+    count = {t['length']: len(fold_references(constants, t['length'])) for t in tasks}
+    for length, n in count.items():
+        if n > FOLD_ALIGN_MAX_REFERENCES:
+            raise SystemExit('%d fold references apply at %d residues: at most %d under --fold_align gapped (--avoid_representatives '
+                             'keeps one per cluster)' % (n, length, FOLD_ALIGN_MAX_REFERENCES))
+    other = [t['length'] for t in tasks if not count[t['length']]]
+    if other:
+        print('skipping lengths without a fold reference that fits them: {}'.format(', '.join(map(str, other))))
+    for length in sorted({t['length'] for t in tasks if count[t['length']]}):
+        dropped = sum(1 for r in refs if not r['template'] and not fold_fits(len(r['xyz']), length))
+        if dropped:
+            print('length {}: {} avoided backbones dropped (outside 4..1024 residues or above 131072 cells)'.format(length, dropped))
+    return [t for t in tasks if count[t['length']]]
+
+
 def fold_potential(constants, length, abar, device):
     """The FoldPotential the constants ask for at this length (its references' names as `.names`), or None when they name no
-    reference.  (Lengths without a reference never get here: fold_lengths drops them when the tasks are made.)"""
+    reference; with --fold_align gapped an AlignedFoldPotential (the references' lengths as `.lengths`).  (Lengths without a
+    reference never get here: fold_lengths drops them when the tasks are made.)"""
     if not has_fold_terms(constants):
         return None
     import numpy as np
-    from .smc import FoldPotential
+    from .smc import AlignedFoldPotential, FoldPotential
     refs = fold_references(constants, length)
+    if fold_gapped(constants):
+        pot = AlignedFoldPotential(length, abar, [r['xyz'] for r in refs], [(r['lo'], r['hi'], r['weight']) for r in refs],
+                                   norm=constants['fold_norm'], n_iter=constants['fold_iterations'], n_rounds=constants['fold_rounds'],
+                                   gap_open=constants['fold_gap_open'], offset_stride=constants['fold_offset_stride'],
+                                   tausq=constants['fold_tausq'], device=device)
+        pot.names, pot.ranges = [r['name'] for r in refs], [(r['lo'], r['hi']) for r in refs]
+        return pot
     pot = FoldPotential(length, abar, np.stack([r['xyz'] for r in refs]), [(r['lo'], r['hi'], r['weight']) for r in refs],
                         n_iter=constants['fold_iterations'], tausq=constants['fold_tausq'], device=device)
     pot.names, pot.ranges = [r['name'] for r in refs], [(r['lo'], r['hi']) for r in refs]
     return pot
 
 
-def write_fold_report(tm, names, ranges, report, directory, length, offset):
+def write_fold_report(tm, names, ranges, report, directory, length, offset, lengths=None, n_aligned=None):
     """One file per sample of a batch, {length}_{offset + i}.txt: a line `ref <name> <tm %.3f> <lo> <hi>` per reference (`names`,
     `ranges`, and row i of `tm` [rows, R], FoldPotential.tm_of of TwistedSampler.last_positions), then a `key value` line per field
-    of `report` (the fold fields of last_shape), %.3f for TM-scores and the energy, %d for counts."""
+    of `report` (the fold fields of last_shape), %.3f for TM-scores and the energy, %d for counts.  With `lengths` (per reference)
+    and `n_aligned` [rows, R] (AlignedFoldPotential.alignment_of) the lines are `ref <name> <tm> <lo> <hi> <length> <n_aligned>`."""
     from .capi import FOLD_COUNTS
     rows = tm.tolist()
-    write_report(report, FOLD_COUNTS, directory, length, offset,
-                 ['\n'.join('ref {} {:.3f} {:g} {:g}'.format(n, v, lo, hi) for n, v, (lo, hi) in zip(names, row, ranges)) for row in rows])
+    if lengths is None:
+        heads = ['\n'.join('ref {} {:.3f} {:g} {:g}'.format(n, v, lo, hi) for n, v, (lo, hi) in zip(names, row, ranges)) for row in rows]
+    else:
+        heads = ['\n'.join('ref {} {:.3f} {:g} {:g} {:d} {:d}'.format(n, v, lo, hi, int(L), int(k))
+                           for n, v, (lo, hi), L, k in zip(names, row, ranges, lengths, counts))
+                 for row, counts in zip(rows, n_aligned.tolist())]
+    write_report(report, FOLD_COUNTS, directory, length, offset, heads)
 
 
 def sum_potentials(*potentials):
@@ -762,7 +850,11 @@ class GuidedRunner(UnconditionalRunner):
                                         os.path.join(outdir, 'binder'), length, offset)
                 if constants['write_complex'] and binder is not None:
                     write_complex(sampler.last_positions.numpy(), constants['target'], os.path.join(outdir, 'complex'), length, offset)
-                if constants['write_fold'] and fold is not None:
+                if constants['write_fold'] and fold is not None and fold_gapped(constants):
+                    found = fold.alignment_of(sampler.last_positions.to(fold.device))
+                    write_fold_report(found['tm'].cpu(), fold.names, fold.ranges, report_fields(sampler.last_shape, capi.FOLD_REPORT),
+                                      os.path.join(outdir, 'fold'), length, offset, fold.lengths, found['n_aligned'].cpu())
+                elif constants['write_fold'] and fold is not None:
                     write_fold_report(fold.tm_of(sampler.last_positions.to(fold.device)).cpu(), fold.names, fold.ranges,
                                       report_fields(sampler.last_shape, capi.FOLD_REPORT), os.path.join(outdir, 'fold'), length, offset)
 

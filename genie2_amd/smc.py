@@ -1506,8 +1506,9 @@ class FoldPotential(_HipPotential):
     potential's device.  `tm_of(x)` is [B, R], every TM-score.
 
     The defaults (tausq = 1 A^2, weights 1) are design choices: no trained checkpoint is in the tree, so their effect on sample
-    quality is unmeasured.  Not built: references of another length or with gaps, per-residue masks on a reference, a
-    best-of-several-templates form, coupling between the particles of a batch."""
+    quality is unmeasured.  References of another length or with gaps are AlignedFoldPotential's (below), which aligns before it
+    scores.  Not built: per-residue masks on a reference, a best-of-several-templates form, coupling between the particles of a
+    batch."""
 
     def __init__(self, n_res, alphas_cumprod, references, bounds, n_iter=16, tausq=1.0, device='cuda'):
         import math
@@ -1554,6 +1555,135 @@ class FoldPotential(_HipPotential):
                    self.n_iter, _ptr(var), *(_ptr(t) for t in outs),
                    *self._workspace(self.lib.genie_fold_potential_work_bytes(B, self.n_res, self.R)))
         return tuple(t for t in outs if t is not None)
+
+
+def _check_aligned_references(references, lengths, n_res):
+    """AlignedFoldPotential's references as (y float32 [R, Nr, 3] on the CPU, padded with zeros and trimmed to the longest chain, the
+    lengths as R ints): a list of [L_r, 3] arrays, or a padded [R, Nr, 3] tensor with `lengths`; a ValueError otherwise."""
+    lo, hi, cells = capi.TM_MIN_LENGTH, capi.TMALIGN_MAX_LENGTH, capi.TMALIGN_MAX_CELLS
+    if lengths is None:
+        try:
+            chains = [torch.as_tensor(c).detach().to(dtype=torch.float32, device='cpu') for c in references]
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('references must be a list of [L, 3] coordinates, or [R, Nr, 3] with lengths=, got %r' % type(references)) from None
+        for r, c in enumerate(chains):
+            if c.dim() != 2 or c.shape[1] != 3:
+                raise ValueError('reference %d must be [L, 3], got %s' % (r, tuple(c.shape)))
+        lengths = [int(c.shape[0]) for c in chains]
+    else:
+        try:
+            padded = torch.as_tensor(references).detach().to(dtype=torch.float32, device='cpu')
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('references must be a list of [L, 3] coordinates, or [R, Nr, 3] with lengths=, got %r' % type(references)) from None
+        if padded.dim() != 3 or padded.shape[2] != 3:
+            raise ValueError('references must be [R, Nr, 3] where lengths is given, got %s' % (tuple(padded.shape),))
+        lengths = lengths.tolist() if torch.is_tensor(lengths) else list(lengths)
+        if len(lengths) != padded.shape[0] or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in lengths):
+            raise ValueError('lengths must hold one integer per reference: %d entries for %d references' % (len(lengths), padded.shape[0]))
+        lengths = [int(v) for v in lengths]
+        if any(v > padded.shape[1] for v in lengths):
+            raise ValueError('lengths holds %d, references has %d rows per chain' % (max(lengths), padded.shape[1]))
+        chains = [padded[r, :max(v, 0)] for r, v in enumerate(lengths)]
+    if not 1 <= len(chains) <= capi.FOLD_ALIGN_MAX_REFERENCES:
+        raise ValueError('references must hold 1..%d backbones, got %d' % (capi.FOLD_ALIGN_MAX_REFERENCES, len(chains)))
+    for r, v in enumerate(lengths):
+        if not lo <= v <= hi:
+            raise ValueError('reference %d has %d residues, the gapped alignment takes %d..%d' % (r, v, lo, hi))
+        if n_res * v > cells:
+            raise ValueError('reference %d has %d residues: n_res (%d) times that is above %d cells' % (r, v, n_res, cells))
+    y = torch.zeros(len(chains), max(lengths), 3, dtype=torch.float32)
+    for r, c in enumerate(chains):
+        if not bool(torch.isfinite(c).all()):
+            raise ValueError('reference %d has a coordinate that is not finite' % r)
+        y[r, :lengths[r]] = c
+    return y, lengths
+
+
+class AlignedFoldPotential(_HipPotential):
+    """Fold guidance under gapped alignment as one HIP entry (genie_fold_align_potential, csrc/fold_align_kernels.hip;
+    include/genie_hip.h states the mathematics): FoldPotential for references of any length.  `pot(x0 [B,N,3], step) -> log p [B]`,
+    differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside the other built-in potentials (SumPotential adds
+    them).  `references` is a list of [L_r, 3] C-alpha backbones of 4..1024 residues each, n_res L_r at most 131072 -- or a padded
+    tensor [R, Nr, 3] with `lengths=` -- and `bounds` one row (lo, hi[, weight]) per reference, as FoldPotential takes them.  Every
+    particle is aligned to every reference exactly as similarity.TMAlign aligns a query to a reference (`norm`, `n_iter`, `n_rounds`,
+    `gap_open` are its arguments; `offset_stride` s visits every s-th offset of the gapless stage and always the last), the winning
+    fit is polished by `n_iter` more ascent steps over the aligned pairs, and with n_r the soft number of superposed residues and
+    Lnorm_r the normalising length
+      E = sum_r weight_r [ max(0, Lnorm_r lo_r - n_r)^2 + max(0, n_r - Lnorm_r hi_r)^2 ],   log p = -E / (2 var),
+    var = xstart_variance(alphas_cumprod[step], tausq) computed on the device.  The gradient holds every pair's alignment and fit
+    fixed: the alignment is piecewise constant in x0, so it is the derivative on the piece the particle lies in (an unaligned residue
+    gets 0), and the envelope theorem covers the fit.  The forward keeps the gradient the kernel computes and the backward scales it.
+
+    Everything is validated on the host before the device is looked at; a potential whose weights are all 0 is a ValueError.
+    `describe(x)` is FoldPotential's report (capi.FOLD_REPORT); `tm_of(x)` is [B, R], every polished TM-score, at least TMAlign's in
+    exact arithmetic; `alignment_of(x)` is a dict of 'map' [B,R,N] int32 (per particle residue the matched reference residue, or -1),
+    'n_aligned' [B,R] int32, 'rot' [B,R,3,3] and 'trans' [B,R,3] (the polished fit, rot x + trans ~ reference), 'rot0' and 'trans0'
+    (the search's fit before the polish) and 'tm' [B,R].
+
+    The defaults (TMAlign's, stride 1, tausq = 1 A^2, weights 1) are design choices: no trained checkpoint is in the tree, so their
+    effect on sample quality is unmeasured.  Not built: gradients across a change of alignment, warm-starting the search from the
+    previous step, tables above 131072 cells, per-residue masks, a best-of-several-templates form."""
+
+    def __init__(self, n_res, alphas_cumprod, references, bounds, norm='query', n_iter=16, n_rounds=8, gap_open=-0.6, offset_stride=1,
+                 tausq=1.0, device='cuda', lengths=None):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or not capi.TM_MIN_LENGTH <= n_res <= capi.TMALIGN_MAX_LENGTH:
+            raise ValueError('n_res must be an integer in %d..%d, got %r' % (capi.TM_MIN_LENGTH, capi.TMALIGN_MAX_LENGTH, n_res))
+        y, lengths = _check_aligned_references(references, lengths, int(n_res))
+        table = check_fold_bounds(bounds, int(y.shape[0]))
+        if norm not in capi.TMALIGN_NORMS:
+            raise ValueError('norm must be one of %s, got %r' % (capi.TMALIGN_NORMS, norm))
+        if isinstance(n_iter, bool) or not isinstance(n_iter, numbers.Integral) or not 1 <= n_iter <= capi.TM_MAX_ITER:
+            raise ValueError('n_iter must be an integer in 1..%d, got %r' % (capi.TM_MAX_ITER, n_iter))
+        if isinstance(n_rounds, bool) or not isinstance(n_rounds, numbers.Integral) or not 0 <= n_rounds <= capi.TMALIGN_MAX_ROUNDS:
+            raise ValueError('n_rounds must be an integer in 0..%d, got %r' % (capi.TMALIGN_MAX_ROUNDS, n_rounds))
+        if isinstance(gap_open, bool) or not isinstance(gap_open, numbers.Real) or not -10.0 <= gap_open <= 0.0:       # (NaN fails both)
+            raise ValueError('gap_open must be a number in -10..0, got %r' % (gap_open,))
+        if (isinstance(offset_stride, bool) or not isinstance(offset_stride, numbers.Integral)
+                or not 1 <= offset_stride <= capi.FOLD_ALIGN_MAX_STRIDE):
+            raise ValueError('offset_stride must be an integer in 1..%d, got %r' % (capi.FOLD_ALIGN_MAX_STRIDE, offset_stride))
+        if not (_is_scalar(tausq) and math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        if not bool((table[:, 2] > 0).any()):
+            raise ValueError('no term enabled: every reference has weight 0')
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.R, self.Nr, self.lengths = int(y.shape[0]), int(y.shape[1]), list(lengths)
+        self.norm, self.n_iter, self.n_rounds = norm, int(n_iter), int(n_rounds)
+        self.gap_open, self.offset_stride = float(gap_open), int(offset_stride)
+        self.references = y.contiguous().to(self.device)
+        self.lr = torch.tensor(lengths, dtype=torch.int32).to(self.device)
+        self.bounds = table.to(torch.float32).contiguous().to(self.device)
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (FoldPotential's), on the potential's device."""
+        return _decode_report(self._launch(self._checked(x), self._one, want='report')['report'], capi.FOLD_REPORT, capi.FOLD_COUNTS)
+
+    def tm_of(self, x):
+        """[B, R] float32 on the potential's device: the polished TM-score of every sample of x [B,N,3] to every reference."""
+        return self._launch(self._checked(x), self._one, want='tm')['tm']
+
+    def alignment_of(self, x):
+        """The alignment of every sample of x [B,N,3] to every reference (the class docstring names the keys), on the potential's device."""
+        return self._launch(self._checked(x), self._one, want='alignment')
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous): (logp, grad) for 'logp', else a dict of the outputs `want` names."""
+        B, N, R = x.shape[0], self.n_res, self.R
+        f32, i32 = dict(dtype=torch.float32, device=x.device), dict(dtype=torch.int32, device=x.device)
+        names = ('logp', 'grad', 'report', 'tm', 'n_aligned', 'map', 'rot', 'trans', 'rot0', 'trans0')
+        make = {'logp': lambda: torch.empty(B, **f32), 'grad': lambda: torch.empty_like(x),
+                'report': lambda: torch.empty(B, len(capi.FOLD_REPORT), **f32), 'tm': lambda: torch.empty(B, R, **f32),
+                'n_aligned': lambda: torch.empty(B, R, **i32), 'map': lambda: torch.empty(B, R, N, **i32),
+                'rot': lambda: torch.empty(B, R, 3, 3, **f32), 'trans': lambda: torch.empty(B, R, 3, **f32),
+                'rot0': lambda: torch.empty(B, R, 3, 3, **f32), 'trans0': lambda: torch.empty(B, R, 3, **f32)}
+        asked = {'logp': ('logp', 'grad'), 'report': ('report',), 'tm': ('tm',),
+                 'alignment': ('tm', 'n_aligned', 'map', 'rot', 'trans', 'rot0', 'trans0')}[want]
+        out = {k: make[k]() for k in asked}
+        self._call('genie_fold_align_potential', self._stream(), B, N, _ptr(x), R, self.Nr, _ptr(self.references), _ptr(self.lr),
+                   _ptr(self.bounds), capi.TMALIGN_NORMS.index(self.norm), self.n_iter, self.n_rounds, self.gap_open, self.offset_stride,
+                   _ptr(var), *(_ptr(out.get(k)) for k in names),
+                   *self._workspace(self.lib.genie_fold_align_potential_work_bytes(B, N, R)))
+        return (out['logp'], out['grad']) if want == 'logp' else out
 
 
 class SumPotential:

@@ -643,6 +643,68 @@ int genie_tm_align(genie_stream_t stream, int M, int Nq, const float* xq /*[M,Nq
                    float* tm, float* rmsd, int* n_aligned, int* rounds /*each [M,R]*/,
                    int* map /*[M,R,Nq] or NULL*/, float* rot /*[M,R,9] or NULL*/, float* trans /*[M,R,3] or NULL*/);
 
+/* The fold potential of twisted-diffusion / SMC sampling under gapped alignment, with its gradient and a per-particle report, without
+ * a handle (csrc/fold_align_kernels.hip): genie_fold_potential with the identity alignment replaced by the alignment genie_tm_align
+ * finds, so that a reference of any length counts and the score guidance pushes on is the score novelty reports.  The reference has
+ * no counterpart.
+ * Particles x0 [B,N,3]; references ref [R,Nr,3], reference r using rows 0..lr[r]-1 (the rest is never read), lr a device int32 array
+ * with 4 <= lr[r] <= Nr, validated by the caller (the kernel clamps it into 4..Nr); bounds [R,3] (device) holds (lo_r, hi_r, weight_r)
+ * as for genie_fold_potential.  norm (0 query, 1 reference, 2 shorter, 3 longer), n_iter, n_rounds and gap_open are genie_tm_align's;
+ * offset_stride s >= 1.  For a pair (b, r), the particle being the query of length N and the reference of length L_r:
+ *   1. Search.  genie_tm_align's procedure for (query x_b, reference y_r) exactly: stage 0, then stages 1..n_rounds, the best stage with
+ *      ties to the earliest -- with one addition: stage 0 visits the offsets 0, s, 2 s, ... and always also the last one, Lb - La, in
+ *      ascending order, ties to the lowest offset as before; at s = 1 the search IS genie_tm_align's.  Its results: the alignment A*
+ *      (the map), the transform T* (rot0, trans0), n_aligned.
+ *   2. Polish.  n_iter more iterations of the same weighted Horn ascent over the pairs of A* only, starting from the weights
+ *      w = g(T*)^2 with g = 1 / (1 + d^2 / d0^2) under T*: every iteration takes the weighted centroids and the proper rotation of its
+ *      weights, forms g under that fit and hands g^2 on.  The LAST iteration is taken, for genie_fold_potential's reason: the fit the
+ *      gradient uses is a fixed one.  n_r = sum over the aligned pairs of g is the soft number of superposed residues, tm_r = n_r /
+ *      Lnorm_r, and (R*, t*) is that fit written as R* x_query + t* ~ x_reference whichever chain moved.  In exact arithmetic the
+ *      ascent is monotone, so n_r / Lnorm_r >= genie_tm_align's tm.
+ *   3. Energy.  E = sum_r weight_r [ max(0, Lnorm_r lo_r - n_r)^2 + max(0, n_r - Lnorm_r hi_r)^2 ],  logp_out[b] = -E / (2 var), var
+ *      one float in device memory.
+ *   4. Gradient, WITH EVERY PAIR'S ALIGNMENT A* AND FIT (R*, t*) HELD FIXED.  For a query residue i aligned to reference residue j:
+ *         e_i = R* x_i + t* - y_j,   d n_r / d x_i = -(2 / d0_r^2) g_i^2 R*^T e_i;   an unaligned residue gets 0;
+ *         grad_out[b,i] = (2 / var) sum_r (k_r / d0_r^2) g_i^2 R*^T e_i,   k_r = weight_r (max(0, n_r - Lnorm_r hi_r) - max(0, Lnorm_r lo_r - n_r)),
+ *      d0_r = d0(Lnorm_r), which differs between references unless norm is 0 (query).
+ *      The alignment is piecewise constant in x, so this is the derivative on the piece the particle lies in: where the alignment
+ *      changes the score has a kink and the gradient says nothing about the other side.  The envelope theorem covers the fit (at a
+ *      converged ascent it maximises n_r over rigid transforms, so holding it fixed gives the total derivative on the piece).  Nothing
+ *      differentiates through the table, the traceback or the iterations.  A reference whose hinges are both inactive, or whose weight
+ *      is 0, contributes exactly 0 to logp and to the gradient.
+ *   5. Report.  report_out[b] holds GENIE_FOLD_REPORT floats with genie_fold_potential's meaning, `N lo` there reading `Lnorm_r lo`
+ *      here: tm_nearest, nearest, tm_lowest_wanted, n_fold_violations, e_fold.
+ * Optional outputs, each may be NULL: tm_out [B,R] (tm_r); n_aligned_out [B,R] int32; map_out [B,R,N] int32, per query residue the
+ * matched reference residue or -1; rot_out [B,R,9] (row-major) and trans_out [B,R,3], given together: the polished fit (R*, t*);
+ * rot0_out and trans0_out, given together: T* before the polish.  logp_out and grad_out are given together or both NULL; at least one
+ * output is asked for.
+ * Two launches on `stream`.  Grid (R, B), 256 threads, one work-group per pair, genie_tm_align's LDS layout (at most 60 KB of dynamic
+ * LDS) and anti-diagonal wavefront; wave 0 runs the polish; the pair's n_r, Lnorm_r, d0_r and fit (20 floats) and its query-indexed map
+ * (N int32, inverted through LDS when the reference moved) go to `work`: genie_fold_align_potential_work_bytes(B, N, R) =
+ * 4 B R (20 + N) bytes, 4-byte aligned (0 for B, N or R out of range).  Grid (ceil(N / 256), B), 256 threads, launched when logp_out
+ * or report_out is given: one thread per query residue walks the references in index order, reads its map entry and the stored fit and
+ * adds the energy, the report and, for references with k_r != 0 only, its residue's share of the gradient.  No allocation, no
+ * synchronisation, no host read, no atomics, no scratch, fixed summation order: two calls on the same inputs are bitwise equal.  Rows
+ * are never read out of range.
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error(NULL) naming this entry and the argument: B outside
+ * 1..65535; N or Nr outside GENIE_TM_MIN_LENGTH..GENIE_TMALIGN_MAX_LENGTH; N * Nr above GENIE_TMALIGN_MAX_CELLS; R outside
+ * 1..GENIE_FOLD_ALIGN_MAX_REFERENCES; norm outside 0..3; n_iter outside 1..GENIE_TM_MAX_ITER; n_rounds outside
+ * 0..GENIE_TMALIGN_MAX_ROUNDS; gap_open not finite, above 0 or below -10; offset_stride outside 1..GENIE_FOLD_ALIGN_MAX_STRIDE; x0,
+ * ref, lr, bounds or var NULL; no output asked for; logp_out without grad_out, rot_out without trans_out, rot0_out without trans0_out
+ * or the other way round; `work` NULL, misaligned or work_bytes too small. */
+#define GENIE_FOLD_ALIGN_MAX_REFERENCES 1024
+#define GENIE_FOLD_ALIGN_MAX_STRIDE 64
+int genie_fold_align_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/,
+                               int R, int Nr, const float* ref /*[R,Nr,3], device*/, const int* lr /*[R] device*/,
+                               const float* bounds /*[R,3] device: lo, hi, weight*/,
+                               int norm, int n_iter, int n_rounds, float gap_open, int offset_stride, const float* var /*[1], device*/,
+                               float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                               float* report_out /*[B,GENIE_FOLD_REPORT] or NULL*/, float* tm_out /*[B,R] or NULL*/,
+                               int* n_aligned_out /*[B,R] or NULL*/, int* map_out /*[B,R,N] or NULL*/,
+                               float* rot_out /*[B,R,9] or NULL*/, float* trans_out /*[B,R,3] or NULL*/,
+                               float* rot0_out /*[B,R,9] or NULL*/, float* trans0_out /*[B,R,3] or NULL*/, void* work, size_t work_bytes);
+size_t genie_fold_align_potential_work_bytes(int B, int N, int R);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
