@@ -132,6 +132,9 @@ SYMBOLS = {
     'genie_fold_align_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 12 + [C.c_size_t]),
     'genie_fold_align_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'genie_diversity_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 6 +
+                                  [C.c_size_t]),
+    'genie_diversity_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -165,6 +168,9 @@ FOLD_REPORT = ('tm_nearest', 'nearest', 'tm_lowest_wanted', 'n_fold_violations',
 FOLD_COUNTS = ('nearest', 'n_fold_violations')
 FOLD_MAX_REFERENCES = 4096      # GENIE_FOLD_MAX_REFERENCES
 FOLD_ALIGN_MAX_REFERENCES, FOLD_ALIGN_MAX_STRIDE = 1024, 64      # GENIE_FOLD_ALIGN_MAX_REFERENCES, _MAX_STRIDE
+DIVERSITY_REPORT = ('tm_nearest_design', 'nearest_design', 'tm_mean_design', 'n_similar', 'e_diversity')      # GENIE_DIVERSITY_REPORT slots
+DIVERSITY_COUNTS = ('nearest_design', 'n_similar')
+DIVERSITY_MAX_BATCH = 1448      # GENIE_DIVERSITY_MAX_BATCH
 TMALIGN_NORMS = ('query', 'reference', 'shorter', 'longer')      # norm 0..3 of genie_tm_align and genie_fold_align_potential
 
 _lib = None

@@ -53,12 +53,17 @@ outdir/complex/{length}_{index}.pdb as that CLI does.
 add fold guidance towards a template backbone or away from known ones, summed after all the others; `--write_fold` writes
 outdir/fold/{length}_{index}.txt as that CLI does, and lengths without a reference of their own length are skipped.  `--fold_align
 gapped` (with `--fold_norm`, `--fold_rounds`, `--fold_gap_open`, `--fold_offset_stride`) scores under gapped alignment instead, so
-that references of any length apply, exactly as that CLI describes."""
+that references of any length apply, exactly as that CLI describes.
+
+`--diversity_tm_max T` (with `--diversity_weight`, `--diversity_iterations`, `--diversity_tausq` and `--write_diversity`: the flags of
+add_diversity_arguments in the same module; it needs `--num_particles`) makes the designs of one device batch repel each other while
+they are sampled, summed last; `--write_diversity` writes outdir/batch_diversity/{length}_{index}.txt as that CLI does.  The coupling
+is within one device batch only: across batches and runs use `--avoid_dir`."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_fold_arguments, add_guidance_arguments,
+from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_diversity_arguments, add_fold_arguments, add_guidance_arguments,
                                          add_secstruct_arguments, add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
 
 
@@ -158,6 +163,7 @@ def build_parser():
     add_symmetry_arguments(p)
     add_binder_arguments(p)
     add_fold_arguments(p)
+    add_diversity_arguments(p)
     return p
 
 

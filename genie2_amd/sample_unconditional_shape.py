@@ -2,7 +2,7 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure, sheet, symmetry, binder or fold term (below), is needed.
+least one of the three, or a secondary-structure, sheet, symmetry, binder, fold or diversity term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -69,12 +69,24 @@ backbones that do not fit are dropped there with a printed count, and more than 
 `--fold_norm query|reference|shorter|longer` (default query, novelty's), `--fold_rounds` (default 8), `--fold_gap_open` (default
 -0.6) and `--fold_offset_stride` (default 1: every offset of the gapless stage) are the alignment's arguments and need
 `--fold_align gapped`; the `ref` lines of `--write_fold` become `ref NAME TM LO HI LENGTH N_ALIGNED`.  Not built: gradients across
-a change of alignment, per-residue masks on a reference, a best-of-several-templates form, coupling between the particles of a
-batch.
+a change of alignment, per-residue masks on a reference, a best-of-several-templates form.
+
+`--diversity_tm_max T` (with `--num_particles K`, which it needs: the run ends without it; K = 1 is valid and gives single coupled
+trajectories) makes the designs of one device batch repel each other while they are sampled: a DiversityPotential
+(csrc/diversity_kernels.hip) scores every pair of particles of different designs once with the fold term's score and keeps it at or
+below T (weight `--diversity_weight`, default 1, divided by K; `--diversity_iterations`, default 16, ascent steps per seed;
+`--diversity_tausq` the likelihood variance).  The particles of one design are resampled copies of each other and do not repel.  The
+term is summed last and is enough on its own.  A design's trajectory then depends on the others of its batch, on purpose.  The coupling
+is within one device batch only (`--batch_size` designs): across batches, devices and runs use `--avoid_dir` on the outputs so far.
+`--write_diversity` adds outdir/batch_diversity/{length}_{index}.txt: a line `design NAME TM` for every other written design of the
+same batch, then one `key value` line per field of DiversityPotential.describe (the nearest design of the batch, the mean, the number
+above T, the energy), every written design counting as one.  Not built: gapped alignment between particles, coupling across batches
+or devices, weighting partners by their SMC weights, a lower hinge.
 
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
-add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments, add_binder_arguments and add_fold_arguments too and then guides
+add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments, add_binder_arguments, add_fold_arguments and
+add_diversity_arguments too and then guides
 with the sum of the potentials asked for."""
 import os
 
@@ -729,6 +741,72 @@ def write_fold_report(tm, names, ranges, report, directory, length, offset, leng
     write_report(report, FOLD_COUNTS, directory, length, offset, heads)
 
 
+DIVERSITY_DEFAULTS = dict(diversity_tm_max=None, diversity_weight=1.0, diversity_iterations=16, diversity_tausq=1.0, write_diversity=False)
+
+
+def add_diversity_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    parser.add_argument('--diversity_tm_max', type=float, default=None,
+                        help='With --num_particles: guide the designs of one device batch to a TM-score of at most this to each other '
+                             'while they are sampled (across batches and runs: --avoid_dir); default: no such term' + tail)
+    parser.add_argument('--diversity_weight', type=float, default=1.0, help='Weight of the diversity term (divided by --num_particles)' + tail)
+    parser.add_argument('--diversity_iterations', type=int, default=16,
+                        help='Ascent iterations per seed of the TM-score between particles, 1..32' + tail)
+    parser.add_argument('--diversity_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the diversity term, Angstrom^2' + tail)
+    parser.add_argument('--write_diversity', action='store_true',
+                        help='Write outdir/batch_diversity/{length}_{index}.txt: the TM-score of every written structure to the others '
+                             'of its batch, the nearest of them, their mean, the number above --diversity_tm_max and the energy' + tail)
+
+
+def diversity_constants(params):
+    """The diversity keys of a runner's constants: the flags of add_diversity_arguments.  A diversity flag without
+    --diversity_tm_max, --diversity_tm_max without --num_particles and a value out of range end the run here."""
+    import math
+    c = {k: params.get(k, v) for k, v in DIVERSITY_DEFAULTS.items()}
+    c['write_diversity'] = bool(c['write_diversity'])
+    if c['diversity_tm_max'] is None:
+        given = [k for k, v in DIVERSITY_DEFAULTS.items() if c[k] != v]
+        if given:
+            raise SystemExit('%s: a diversity flag needs --diversity_tm_max, the TM-score to stay below' % ', '.join('--' + k for k in given))
+        return c
+    if params.get('num_particles') is None:
+        raise SystemExit('--diversity_tm_max needs --num_particles: the designs of a batch repel each other as particle systems '
+                         '(--num_particles 1 gives single coupled trajectories)')
+    if not 0 < c['diversity_tm_max'] <= 1:
+        raise SystemExit('--diversity_tm_max must be in (0, 1], got %r' % (c['diversity_tm_max'],))
+    if not (math.isfinite(c['diversity_weight']) and c['diversity_weight'] > 0):
+        raise SystemExit('--diversity_weight must be finite and > 0, got %r' % (c['diversity_weight'],))
+    if not 1 <= c['diversity_iterations'] <= 32:
+        raise SystemExit('--diversity_iterations must be in 1..32, got %r' % (c['diversity_iterations'],))
+    if not (math.isfinite(c['diversity_tausq']) and c['diversity_tausq'] > 0):
+        raise SystemExit('--diversity_tausq must be finite and > 0, got %r' % (c['diversity_tausq'],))
+    return c
+
+
+def has_diversity_terms(constants):
+    return constants.get('diversity_tm_max') is not None
+
+
+def diversity_potential(constants, length, abar, device):
+    """The DiversityPotential the constants ask for at this length, over systems of --num_particles, or None when they ask for no
+    such term."""
+    if not has_diversity_terms(constants):
+        return None
+    from .smc import DiversityPotential
+    return DiversityPotential(length, abar, constants['num_particles'], tm_max=constants['diversity_tm_max'],
+                              weight=constants['diversity_weight'], n_iter=constants['diversity_iterations'],
+                              tausq=constants['diversity_tausq'], device=device)
+
+
+def write_diversity_report(tm, names, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a line `design <name> <tm %.3f>` for every other design of the batch
+    (`names`, and row i of `tm` [rows, rows], DiversityPotential.tm_of of TwistedSampler.last_positions), then a `key value` line per
+    field of `report` (the diversity fields of last_shape), %.3f for TM-scores and the energy, %d for counts."""
+    from .capi import DIVERSITY_COUNTS
+    heads = ['\n'.join('design {} {:.3f}'.format(n, v) for k, (n, v) in enumerate(zip(names, row)) if k != i) for i, row in enumerate(tm.tolist())]
+    write_report(report, DIVERSITY_COUNTS, directory, length, offset, heads)
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -773,8 +851,8 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, symmetry, binder and fold potentials the
-    constants ask for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, symmetry, binder, fold and diversity
+    potentials the constants ask for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
 
     def guided_lengths(self, tasks, params):
         """The tasks whose length the restraints, the blueprint, the ladder, the symmetric layout and the fold references allow."""
@@ -795,6 +873,7 @@ class GuidedRunner(UnconditionalRunner):
         c.update(symmetry_constants(params))
         c.update(binder_constants(params))
         c.update(fold_constants(params))
+        c.update(diversity_constants(params))
         return c
 
     def batch_potentials(self, constants, length, abar, device):
@@ -819,13 +898,14 @@ class GuidedRunner(UnconditionalRunner):
             symmetry = symmetry_potential(constants, length, abar, device)
             binder = binder_potential(constants, length, abar, device)
             fold = fold_potential(constants, length, abar, device)
+            diversity = diversity_potential(constants, length, abar, device)
             chains = {'chain_lengths': symmetry.chain_lengths()} if constants['unit_chains'] else {}
             for batch, offset in self.batches(constants, outdir, length):
                 sampler.sample({
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
                     'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet,
-                                                        symmetry, binder, fold),
+                                                        symmetry, binder, fold, diversity),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **chains, **self.partial_params(constants)})
@@ -857,18 +937,23 @@ class GuidedRunner(UnconditionalRunner):
                 elif constants['write_fold'] and fold is not None:
                     write_fold_report(fold.tm_of(sampler.last_positions.to(fold.device)).cpu(), fold.names, fold.ranges,
                                       report_fields(sampler.last_shape, capi.FOLD_REPORT), os.path.join(outdir, 'fold'), length, offset)
+                if constants['write_diversity'] and diversity is not None:
+                    write_diversity_report(diversity.tm_of(sampler.last_positions.to(diversity.device)).cpu(),
+                                           ['{}_{}'.format(length, offset + i) for i in range(len(sampler.last_positions))],
+                                           report_fields(sampler.last_shape, capi.DIVERSITY_REPORT),
+                                           os.path.join(outdir, 'batch_diversity'), length, offset)
 
 
 class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
         if not (has_shape_terms(c) or has_secstruct_terms(c) or has_sheet_terms(c) or has_symmetry_terms(c) or has_binder_terms(c)
-                or has_fold_terms(c)):
+                or has_fold_terms(c) or has_diversity_terms(c)):
             raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
                              'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target), a sheet term '
                              '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file), a binder term (--target_pdb '
-                             'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance), a fold term (--template_pdb, --avoid_dir) '
-                             'or --symmetry')
+                             'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance), a fold term (--template_pdb, --avoid_dir), '
+                             'a diversity term (--diversity_tm_max with --num_particles) or --symmetry')
         return c
 
 
@@ -882,6 +967,7 @@ def build_parser():
     add_symmetry_arguments(p)
     add_binder_arguments(p)
     add_fold_arguments(p)
+    add_diversity_arguments(p)
     return p
 
 

@@ -9,7 +9,9 @@ gyration, clashes, distance restraints; not in the reference) is the second buil
 is not differentiable) the third, SheetPotential (csrc/sheet_kernels.hip: antiparallel / parallel strand pairing and a ladder of listed
 rungs; not in the reference) the fourth, SymmetryPotential (csrc/symmetry_kernels.hip: cyclic, dihedral and repeat symmetry by
 superposing units under the group's generators; not in the reference) the fifth, BinderPotential (csrc/binder_kernels.hip: contacts,
-hotspot coverage and clashes against a fixed target that is not sampled; not in the reference) the sixth, and SumPotential adds potentials.
+hotspot coverage and clashes against a fixed target that is not sampled; not in the reference) the sixth, FoldPotential and
+AlignedFoldPotential (csrc/fold_kernels.hip, fold_align_kernels.hip: TM-score ranges to fixed backbones) and DiversityPotential
+(csrc/diversity_kernels.hip: the particles of a batch repel each other) follow, and SumPotential adds potentials.
 
 The reference module imports wandb / Bio, which are not installed here, so it could not be run: parity of this file is
 UNPINNED by reference outputs; what is tested is (a) the helpers against restatements of the quoted lines, (b) that a constant
@@ -1507,8 +1509,8 @@ class FoldPotential(_HipPotential):
 
     The defaults (tausq = 1 A^2, weights 1) are design choices: no trained checkpoint is in the tree, so their effect on sample
     quality is unmeasured.  References of another length or with gaps are AlignedFoldPotential's (below), which aligns before it
-    scores.  Not built: per-residue masks on a reference, a best-of-several-templates form, coupling between the particles of a
-    batch."""
+    scores.  Coupling between the particles of a batch is DiversityPotential's.  Not built: per-residue masks on a reference, a
+    best-of-several-templates form."""
 
     def __init__(self, n_res, alphas_cumprod, references, bounds, n_iter=16, tausq=1.0, device='cuda'):
         import math
@@ -1684,6 +1686,84 @@ class AlignedFoldPotential(_HipPotential):
                    _ptr(var), *(_ptr(out.get(k)) for k in names),
                    *self._workspace(self.lib.genie_fold_align_potential_work_bytes(B, N, R)))
         return (out['logp'], out['grad']) if want == 'logp' else out
+
+
+class DiversityPotential(_HipPotential):
+    """Diversity guidance as one HIP entry (genie_diversity_potential, csrc/diversity_kernels.hip; include/genie_hip.h states the
+    mathematics): `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside
+    the other built-in potentials (SumPotential adds them).  The particles of one device batch repel each other: the batch is
+    S = B / num_particles particle systems, system-major as TwistedSampler lays them out (particle b belongs to system
+    b // num_particles), and every pair of particles of DIFFERENT systems is scored once with FoldPotential's score (the particle of
+    the lower index moving, `n_iter` iterations per seed).  With n_bj the soft number of superposed residues of particles b and j,
+      E_b = (weight / num_particles) sum_{j in other systems} max(0, n_bj - N tm_max)^2,   log p_b = -E_b / (2 var),
+    var = xstart_variance(alphas_cumprod[step], tausq) computed on the device, so nothing on the per-step path reads device memory
+    from the host.  The gradient of log p_b is taken in x_b alone, every other particle and every pair's fit held fixed: each
+    particle's own twisting function, with its neighbours as parameters.  Particles of one system are resampled copies of each other
+    and do not repel.
+
+    A system's step now depends on its batch neighbours, on purpose: that is what the term is for, and it is the one built-in
+    potential of which this is true (weights, resampling and the gradient cap stay per system).  The coupling is within one device
+    batch only; across batches and runs, avoid the earlier outputs with a FoldPotential.  The potential is meant for `num_particles`
+    runs (TwistedSampler's 'num_particles', 1 included: single coupled trajectories): without them the whole batch is one system,
+    and one system spanning the whole batch has nothing to repel -- log p and the gradient are exactly 0.
+
+    Everything is validated on the host before the device is looked at.  `pot(x0, step)` takes B a multiple of `num_particles`
+    (ValueError otherwise).  `describe(x)` and `tm_of(x)` score EVERY ROW OF x AS A DESIGN OF ITS OWN (one particle per system),
+    which is what TwistedSampler's reports call them on -- the returned structures, be they every system's best particle or all of
+    them: `describe` gives the names of capi.DIVERSITY_REPORT, 'tm_nearest_design' (the largest TM to another design; 0 for a single
+    row), 'nearest_design' (its row, int64; -1 for a single row), 'tm_mean_design', 'n_similar' (designs above tm_max, int64),
+    'e_diversity' (E with num_particles = 1): [B] tensors on the potential's device; `tm_of` is [B, B], symmetric, 0 on the diagonal.
+
+    The defaults (tm_max 0.5, weight 1, tausq = 1 A^2) are design choices: no trained checkpoint is in the tree, so their effect on
+    sample quality is unmeasured.  Not built: gapped alignment between particles, coupling across batches or devices, weighting
+    partners by their SMC weights, a lower hinge."""
+
+    def __init__(self, n_res, alphas_cumprod, num_particles, tm_max=0.5, weight=1.0, n_iter=16, tausq=1.0, device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or not capi.TM_MIN_LENGTH <= n_res <= capi.TM_MAX_LENGTH:
+            raise ValueError('n_res must be an integer in %d..%d, got %r' % (capi.TM_MIN_LENGTH, capi.TM_MAX_LENGTH, n_res))
+        if isinstance(num_particles, bool) or not isinstance(num_particles, numbers.Integral) or not 1 <= num_particles <= SMC_MAX_PARTICLES:
+            raise ValueError('num_particles must be an integer in 1..%d, got %r' % (SMC_MAX_PARTICLES, num_particles))
+        if not (_is_scalar(tm_max) and 0 < float(tm_max) <= 1):
+            raise ValueError('tm_max must be in (0, 1], got %r' % (tm_max,))
+        if not (_is_scalar(weight) and math.isfinite(float(weight)) and float(weight) > 0):
+            raise ValueError('weight must be finite and > 0, got %r' % (weight,))
+        if isinstance(n_iter, bool) or not isinstance(n_iter, numbers.Integral) or not 1 <= n_iter <= capi.TM_MAX_ITER:
+            raise ValueError('n_iter must be an integer in 1..%d, got %r' % (capi.TM_MAX_ITER, n_iter))
+        if not (_is_scalar(tausq) and math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.K, self.tm_max, self.weight, self.n_iter = int(num_particles), float(tm_max), float(weight), int(n_iter)
+
+    def _checked(self, x0, K=None):
+        x = super()._checked(x0)
+        K = self.K if K is None else K
+        if x.shape[0] < 1 or x.shape[0] % K:
+            raise ValueError('x0 must hold a multiple of num_particles = %d rows, got %d' % (K, x.shape[0]))
+        if x.shape[0] > capi.DIVERSITY_MAX_BATCH:
+            raise ValueError('x0 must hold at most %d rows, got %d' % (capi.DIVERSITY_MAX_BATCH, x.shape[0]))
+        return x
+
+    def describe(self, x):
+        """The report of every row of x [B,N,3] as a design of its own (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x, 1), self._one, want='report', K=1)         # (the energy does not depend on var)
+        return _decode_report(report, capi.DIVERSITY_REPORT, capi.DIVERSITY_COUNTS)
+
+    def tm_of(self, x):
+        """[B, B] float32 on the potential's device: the TM-score of every row of x [B,N,3] to every other, 0 on the diagonal."""
+        return self._launch(self._checked(x, 1), self._one, want='tm', K=1)[0]
+
+    def _launch(self, x, var, want='logp', K=None):
+        """One call of the C entry on x (f32, contiguous) as systems of K (default: num_particles): (logp, grad), (report [B, 5],)
+        or (tm_out [B, B],) as `want` says."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        K = self.K if K is None else K
+        outs = {'logp': lambda: [torch.empty(B, **f32), torch.empty_like(x), None, None],
+                'report': lambda: [None, None, torch.empty(B, len(capi.DIVERSITY_REPORT), **f32), None],
+                'tm': lambda: [None, None, None, torch.empty(B, B, **f32)]}[want]()
+        self._call('genie_diversity_potential', self._stream(), B, K, self.n_res, _ptr(x), self.tm_max, self.weight, self.n_iter,
+                   _ptr(var), *(_ptr(t) for t in outs), *self._workspace(self.lib.genie_diversity_potential_work_bytes(B, K, self.n_res)))
+        return tuple(t for t in outs if t is not None)
 
 
 class SumPotential:

@@ -705,6 +705,50 @@ int genie_fold_align_potential(genie_stream_t stream, int B, int N, const float*
                                float* rot0_out /*[B,R,9] or NULL*/, float* trans0_out /*[B,R,3] or NULL*/, void* work, size_t work_bytes);
 size_t genie_fold_align_potential_work_bytes(int B, int N, int R);
 
+/* The diversity potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle
+ * (csrc/diversity_kernels.hip): the particles of one batch repel each other, so that the designs of one run do not come out as
+ * near-copies.  It is genie_fold_potential with the batch itself for the references.  The reference has no counterpart.
+ * The batch is x0 [B,N,3], 1 <= B <= GENIE_DIVERSITY_MAX_BATCH, GENIE_TM_MIN_LENGTH <= N <= GENIE_TM_MAX_LENGTH, laid out system-major:
+ * K in 1..64 divides B, S = B / K, sys(b) = b / K (genie_smc_reweight's layout).  The constants are tm_max in (0, 1], weight > 0,
+ * n_iter and var (one float in device memory).  d0 = d0(N); the GENIE_TM_SEEDS seed windows are those of genie_pairwise_tm.
+ * Pairs.  For every i < j with sys(i) != sys(j), genie_fold_potential's procedure exactly, x_i the particle (it moves) and x_j the
+ * reference: GENIE_TM_SEEDS seeds, n_iter iterations each, the value sum_n g_n of the LAST iteration, the best seed (ties to the
+ * lowest) giving n_ij and the fit (R, c_p, c_q).  n_ji := n_ij: every unordered pair is scored once, and its one fit serves both
+ * members (in float64 the score with j moving instead is the same to 1e-14 N on the test inputs).  Particles of one system are
+ * resampled copies of each other and are not scored.  tm_out [B,B], optional, receives n_ij / N at [i,j] and at [j,i] and 0 at the
+ * same-system entries, the diagonal included; all of it is written on every call.
+ * Energy.  a_bj = max(0, n_bj - N tm_max);  E_b = (weight / K) sum_{j: sys(j) != sys(b)} a_bj^2;  logp_out[b] = -E_b / (2 var).
+ * Gradient.  grad_out[b,n] = d logp_b / d x_{b,n} WITH EVERY OTHER PARTICLE AND EVERY FIT HELD FIXED: the particle's own twisting
+ * function, the others being parameters.  With c = 2 weight / (K var d0^2) and g_n = 1 / (1 + |e_n|^2 / d0^2):
+ *   j > b (b moved in the pair's fit):          e_n = R (x_{b,n} - c_p) - (x_{j,n} - c_q),   + c a_bj g_n^2 R^T e_n
+ *   j < b (b was the reference of pair (j, b)): e_n = R (x_{j,n} - c_p) - (x_{b,n} - c_q),   - c a_bj g_n^2 e_n
+ * A pair with a_bj = 0 contributes exactly 0.  With S = 1, logp and grad are exactly 0 and nothing is fitted.
+ * report_out[b] holds GENIE_DIVERSITY_REPORT floats: tm_nearest_design (the largest n_bj / N over the scored partners; 0 when there
+ * is none), nearest_design (the lowest j that attains it; -1 when there is none), tm_mean_design (the mean over the scored partners;
+ * 0 when there is none), n_similar (partners with a_bj > 0), e_diversity (E_b, before the division by 2 var); counts are stored as
+ * floats.  logp_out and grad_out are given together or both NULL; report_out and tm_out may be given alone; at least one output is
+ * asked for.
+ * Two launches on `stream`.  One 256-thread work-group per unordered pair (pair (i, j), i < j, is work-group and slot
+ * j (j - 1) / 2 + i; a pair inside one system returns at once), 24 N + 344 bytes of dynamic LDS, the arithmetic of
+ * genie_fold_potential's fit kernel operation for operation: thread 0 writes n, the seed, the fit and the two staged centroids, 24
+ * floats, to the pair's slot of `work` (genie_diversity_potential_work_bytes(B, K, N) = 96 max(1, B (B - 1) / 2) bytes, 4-byte
+ * aligned; 0 for sizes this entry refuses) and both tm_out entries; it is skipped when S = 1.  Grid (ceil(N / 256), B), 256 threads,
+ * one thread per residue: it walks the partners j in index order, looks the pair's fit up and adds the energy, the report and, for
+ * pairs with a_bj > 0 only, the moving-side or reference-side term; thread 0 of tile 0 writes logp, the report and tm_out's zeros.
+ * No allocation, no synchronisation, no host read, no atomics, no scratch: every output is written once in a fixed order, so two calls
+ * on the same inputs are bitwise equal.  Rows n >= N and the same-system slots of `work` are never read.
+ * Returns GENIE_E_ARG, before anything is launched, with genie_last_error(NULL) naming this entry and the argument: B outside
+ * 1..GENIE_DIVERSITY_MAX_BATCH (so that B (B - 1) / 2 <= 2^20 pairs and 96 MB of work); K outside 1..64 or not dividing B; N outside
+ * GENIE_TM_MIN_LENGTH..GENIE_TM_MAX_LENGTH; n_iter outside 1..GENIE_TM_MAX_ITER; tm_max not in (0, 1]; weight not finite or negative;
+ * x0 or var NULL; no output asked for; logp_out and grad_out not given together; `work` NULL, misaligned or work_bytes too small. */
+#define GENIE_DIVERSITY_REPORT 5     /* tm_nearest_design, nearest_design, tm_mean_design, n_similar, e_diversity */
+#define GENIE_DIVERSITY_MAX_BATCH 1448
+int genie_diversity_potential(genie_stream_t stream, int B, int K, int N, const float* x0 /*[B,N,3]*/, float tm_max, float weight,
+                              int n_iter, const float* var /*[1], device*/, float* logp_out /*[B] or NULL*/,
+                              float* grad_out /*[B,N,3] or NULL*/, float* report_out /*[B,GENIE_DIVERSITY_REPORT] or NULL*/,
+                              float* tm_out /*[B,B] or NULL*/, void* work, size_t work_bytes);
+size_t genie_diversity_potential_work_bytes(int B, int K, int N);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
