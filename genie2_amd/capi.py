@@ -135,6 +135,9 @@ SYMBOLS = {
     'genie_diversity_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 6 +
                                   [C.c_size_t]),
     'genie_diversity_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'genie_burial_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 3 +
+                               [C.c_float] * 3 + [C.c_void_p] * 6 + [C.c_size_t]),
+    'genie_burial_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -171,6 +174,10 @@ FOLD_ALIGN_MAX_REFERENCES, FOLD_ALIGN_MAX_STRIDE = 1024, 64      # GENIE_FOLD_AL
 DIVERSITY_REPORT = ('tm_nearest_design', 'nearest_design', 'tm_mean_design', 'n_similar', 'e_diversity')      # GENIE_DIVERSITY_REPORT slots
 DIVERSITY_COUNTS = ('nearest_design', 'n_similar')
 DIVERSITY_MAX_BATCH = 1448      # GENIE_DIVERSITY_MAX_BATCH
+BURIAL_REPORT = ('burial_mean', 'burial_min', 'burial_max', 'n_burial_violated', 'max_burial_violation', 'e_burial_target',
+                 'e_burial_mean')      # GENIE_BURIAL_REPORT slots
+BURIAL_COUNTS = ('n_burial_violated',)
+BURIAL_MAX_LENGTH = 1728        # GENIE_BURIAL_MAX_LENGTH
 TMALIGN_NORMS = ('query', 'reference', 'shorter', 'longer')      # norm 0..3 of genie_tm_align and genie_fold_align_potential
 
 _lib = None

@@ -58,12 +58,18 @@ that references of any length apply, exactly as that CLI describes.
 `--diversity_tm_max T` (with `--diversity_weight`, `--diversity_iterations`, `--diversity_tausq` and `--write_diversity`: the flags of
 add_diversity_arguments in the same module; it needs `--num_particles`) makes the designs of one device batch repel each other while
 they are sampled, summed last; `--write_diversity` writes outdir/batch_diversity/{length}_{index}.txt as that CLI does.  The coupling
-is within one device batch only: across batches and runs use `--avoid_dir`."""
+is within one device batch only: across batches and runs use `--avoid_dir`.
+
+`--bury RANGES --bury_min C`, `--expose RANGES --expose_max C`, `--burial_file`, `--burial_mean_min` / `--burial_mean_max` (with
+`--burial_weight`, `--burial_mean_weight`, `--burial_radius`, `--burial_width`, `--burial_separation`, `--burial_tausq` and
+`--write_burial`: the flags of add_burial_arguments in the same module) add burial guidance by half-sphere exposure, summed after the
+sheet term and before symmetry; `--write_burial` writes outdir/burial/{length}_{index}.txt as that CLI does.  The listed residues are
+positions of the design, not of the motif: a motif's placement moves per particle and the targets do not follow it."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_diversity_arguments, add_fold_arguments, add_guidance_arguments,
+from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_burial_arguments, add_diversity_arguments, add_fold_arguments, add_guidance_arguments,
                                          add_secstruct_arguments, add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
 
 
@@ -164,6 +170,7 @@ def build_parser():
     add_binder_arguments(p)
     add_fold_arguments(p)
     add_diversity_arguments(p)
+    add_burial_arguments(p)
     return p
 
 

@@ -2,7 +2,8 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure, sheet, symmetry, binder, fold or diversity term (below), is needed.
+least one of the three, or a secondary-structure, sheet, symmetry, binder, fold or diversity term (below), or a burial term (below),
+is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -83,10 +84,26 @@ same batch, then one `key value` line per field of DiversityPotential.describe (
 above T, the energy), every written design counting as one.  Not built: gapped alignment between particles, coupling across batches
 or devices, weighting partners by their SMC weights, a lower hinge.
 
+`--bury RANGES --bury_min C` and `--expose RANGES --expose_max C` (RANGES like `3,10-20,35`: 0-based residues, inclusive) tell inside
+from outside: a BurialPotential (csrc/burial_kernels.hip) keeps the half-sphere exposure of the listed residues -- the soft number of
+C-alpha atoms within `--burial_radius` (default 10 A) on the side the virtual C-beta direction 2 x_n - x_{n-1} - x_{n+1} points to,
+residues closer than `--burial_separation` (default 3) in sequence left out, the half-space `--burial_width` (default 2 A) soft -- at
+or above C (a catalytic residue, the hydrophobic face of a helix) or at or below C (an epitope, a binding face).  `--burial_file FILE`
+lists residues one per line, `i lo hi [weight]` (0-based, `inf` allowed for hi, `#` starts a comment); `--burial_weight` scales every
+per-residue weight.  `--burial_mean_min` / `--burial_mean_max` keep the mean count over the chain in a range (weight
+`--burial_mean_weight`; only a max leaves the min at 0, only a min leaves the mean unbounded above): a design with a core, not merely
+a small one.  `--burial_tausq` is the likelihood variance.  The term is summed after the sheet term and before symmetry, and is enough
+on its own.  `--bury` without `--bury_min`, `--expose` without `--expose_max`, a residue named by two sources, and a burial flag
+without a term (`--burial_file`, `--bury`, `--expose`, `--burial_mean_min` or `--burial_mean_max`) end the run; a length too short for
+a listed residue is skipped.  `--write_burial` adds outdir/burial/{length}_{index}.txt: a line `residue I C LO HI` per residue of the
+written structure (its count, and the range asked of it or `- -`), then one `key value` line per field of BurialPotential.describe.
+Not built: tying targets to a motif's placement, chain breaks under `--unit_chains` (the direction stencil crosses them), a full-atom
+or C-beta model, counting a binder target's atoms as neighbours.
+
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
 add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments, add_binder_arguments, add_fold_arguments and
-add_diversity_arguments too and then guides
+add_diversity_arguments and add_burial_arguments too and then guides
 with the sum of the potentials asked for."""
 import os
 
@@ -807,6 +824,135 @@ def write_diversity_report(tm, names, report, directory, length, offset):
     write_report(report, DIVERSITY_COUNTS, directory, length, offset, heads)
 
 
+BURIAL_DEFAULTS = dict(burial_file=None, bury=None, bury_min=None, expose=None, expose_max=None, burial_mean_min=None, burial_mean_max=None,
+                       burial_weight=1.0, burial_mean_weight=1.0, burial_radius=10.0, burial_width=2.0, burial_separation=3, burial_tausq=1.0,
+                       write_burial=False)
+BURIAL_TERM_FLAGS = ('burial_file', 'bury', 'expose', 'burial_mean_min', 'burial_mean_max')     # any of them makes a term
+
+
+def add_burial_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    parser.add_argument('--burial_file', type=str, default=None,
+                        help='Half-sphere exposure targets, one `i lo hi [weight]` line per residue (0-based; hi may be inf); default: '
+                             'no such term' + tail)
+    parser.add_argument('--bury', type=str, default=None,
+                        help='Residues to bury, e.g. 3,10-20,35 (0-based, inclusive): their soft half-sphere count is guided to at least '
+                             '--bury_min' + tail)
+    parser.add_argument('--bury_min', type=float, default=None, help='The count --bury asks for at least' + tail)
+    parser.add_argument('--expose', type=str, default=None,
+                        help='Residues to keep solvent-exposed, e.g. 30-41: their soft half-sphere count is guided to at most '
+                             '--expose_max' + tail)
+    parser.add_argument('--expose_max', type=float, default=None, help='The count --expose allows at most' + tail)
+    parser.add_argument('--burial_mean_min', type=float, default=None,
+                        help='Guide the mean soft half-sphere count over the chain above this; default: no such bound' + tail)
+    parser.add_argument('--burial_mean_max', type=float, default=None,
+                        help='Guide the mean soft half-sphere count over the chain below this; default: no such bound' + tail)
+    parser.add_argument('--burial_weight', type=float, default=1.0, help='Scales the weight of every per-residue burial target' + tail)
+    parser.add_argument('--burial_mean_weight', type=float, default=1.0, help='Weight of the mean-burial term' + tail)
+    parser.add_argument('--burial_radius', type=float, default=10.0,
+                        help='C-alpha distance in Angstrom at which a residue counts half a neighbour' + tail)
+    parser.add_argument('--burial_width', type=float, default=2.0, help='Softness of the half-space in Angstrom' + tail)
+    parser.add_argument('--burial_separation', type=int, default=3,
+                        help='Residues at least this far apart in sequence count as neighbours' + tail)
+    parser.add_argument('--burial_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the burial terms' + tail)
+    parser.add_argument('--write_burial', action='store_true',
+                        help='Write outdir/burial/{length}_{index}.txt: the soft half-sphere count of every residue of every written '
+                             'structure with the range asked of it, then the mean, extremes, violations and energies' + tail)
+
+
+def burial_constants(params):
+    """The burial keys of a runner's constants: the flags of add_burial_arguments, and 'burial_targets', the residues of --burial_file,
+    --bury and --expose as one list [(i, lo, hi, weight), ...] sorted by residue, every weight scaled by --burial_weight, and
+    'burial_mean' = (min, max) or None (one of the two given: the other is 0 / inf).  --bury or --expose without its threshold (or
+    the threshold without its list), a residue named by two sources, a burial flag without a term, a value out of range and a file or
+    a list that does not hold up end the run here."""
+    import math
+    from .smc import check_burial_targets, load_burial_targets, parse_residue_ranges
+    c = {k: params.get(k, v) for k, v in BURIAL_DEFAULTS.items()}
+    c['write_burial'] = bool(c['write_burial'])
+    c['burial_targets'], c['burial_mean'] = [], None
+    if all(c[k] is None for k in BURIAL_TERM_FLAGS):
+        given = [k for k, v in BURIAL_DEFAULTS.items() if c[k] != v]
+        if given:
+            raise SystemExit('%s: a burial flag needs a term: --burial_file, --bury, --expose, --burial_mean_min or --burial_mean_max'
+                             % ', '.join('--' + k for k in given))
+        return c
+    for ranges, bound in (('bury', 'bury_min'), ('expose', 'expose_max')):
+        if c[ranges] is not None and c[bound] is None:
+            raise SystemExit('--%s needs --%s, the count to stay %s' % (ranges, bound, 'at or above' if ranges == 'bury' else 'at or below'))
+        if c[bound] is not None and c[ranges] is None:
+            raise SystemExit('--%s needs --%s, the residues it is about' % (bound, ranges))
+    for k in ('bury_min', 'expose_max', 'burial_mean_min', 'burial_mean_max', 'burial_weight', 'burial_mean_weight'):
+        if c[k] is not None and not (math.isfinite(c[k]) and c[k] >= 0):
+            raise SystemExit('--%s must be finite and >= 0, got %r' % (k, c[k]))
+    for k in ('burial_radius', 'burial_width', 'burial_tausq'):
+        if not (math.isfinite(c[k]) and c[k] > 0):
+            raise SystemExit('--%s must be finite and > 0, got %r' % (k, c[k]))
+    if c['burial_separation'] < 1:
+        raise SystemExit('--burial_separation must be at least 1, got %r' % (c['burial_separation'],))
+    targets = []
+    try:
+        if c['burial_file'] is not None:
+            targets += load_burial_targets(c['burial_file'])
+        if c['bury'] is not None:
+            targets += [(i, c['bury_min'], math.inf, 1.0) for i in parse_residue_ranges(c['bury'])]
+        if c['expose'] is not None:
+            targets += [(i, 0.0, c['expose_max'], 1.0) for i in parse_residue_ranges(c['expose'])]
+        seen = set()
+        for t in targets:
+            if t[0] in seen:
+                raise ValueError('residue %d is named twice (by --burial_file, --bury or --expose)' % t[0])
+            seen.add(t[0])
+        top = 1 + max([t[0] for t in targets if isinstance(t[0], int)], default=0)
+        targets = check_burial_targets([(i, lo, hi, w * c['burial_weight']) for i, lo, hi, w in targets], top)
+    except (OSError, ValueError) as e:
+        raise SystemExit('--burial_file / --bury / --expose: %s' % e) from None
+    c['burial_targets'] = targets
+    lo, hi = c['burial_mean_min'], c['burial_mean_max']
+    if lo is not None or hi is not None:
+        c['burial_mean'] = (0.0 if lo is None else lo, math.inf if hi is None else hi)
+        if c['burial_mean'][1] < c['burial_mean'][0]:
+            raise SystemExit('--burial_mean_max is below --burial_mean_min: %r < %r' % (hi, lo))
+    if not targets and (c['burial_mean'] is None or c['burial_mean_weight'] == 0):
+        raise SystemExit('the burial flags name no residue and no mean with a weight: nothing to guide')
+    return c
+
+
+def has_burial_terms(constants):
+    return bool(constants.get('burial_targets')) or constants.get('burial_mean') is not None
+
+
+def burial_lengths(tasks, targets):
+    """The tasks long enough for every listed residue; the others are skipped with one printed line."""
+    need = 1 + max([t[0] for t in targets], default=-1)
+    short = [t['length'] for t in tasks if t['length'] < need]
+    if short:
+        print('skipping lengths shorter than the {} residues the burial targets name: {}'.format(need, ', '.join(map(str, short))))
+    return [t for t in tasks if t['length'] >= need]
+
+
+def burial_potential(constants, length, abar, device):
+    """The BurialPotential the constants ask for at this length, or None when they ask for no term.  (Lengths too short for a listed
+    residue never get here: burial_lengths drops them when the tasks are made.)"""
+    if not has_burial_terms(constants):
+        return None
+    from .smc import BurialPotential
+    return BurialPotential(length, abar, targets=constants['burial_targets'] or None, mean=constants['burial_mean'],
+                           mean_weight=constants['burial_mean_weight'], radius=constants['burial_radius'], width=constants['burial_width'],
+                           separation=constants['burial_separation'], tausq=constants['burial_tausq'], device=device)
+
+
+def write_burial_report(burial, targets, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a line `residue I C LO HI` per residue (row i of `burial` [rows, N],
+    BurialPotential.burial_of of TwistedSampler.last_positions, %.3f; LO and HI from `targets` [(i, lo, hi, weight), ...], `-` where
+    the residue has none), then a `key value` line per field of `report` (the burial fields of last_shape), %.3f for counts of
+    neighbours and energies, %d for the number of violations."""
+    from .capi import BURIAL_COUNTS
+    ranges = {t[0]: ('{:g}'.format(t[1]), '{:g}'.format(t[2])) for t in targets}
+    heads = ['\n'.join('residue {} {:.3f} {} {}'.format(n, v, *ranges.get(n, ('-', '-'))) for n, v in enumerate(row)) for row in burial.tolist()]
+    write_report(report, BURIAL_COUNTS, directory, length, offset, heads)
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -851,13 +997,15 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, symmetry, binder, fold and diversity
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, burial, symmetry, binder, fold and diversity
     potentials the constants ask for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
 
     def guided_lengths(self, tasks, params):
-        """The tasks whose length the restraints, the blueprint, the ladder, the symmetric layout and the fold references allow."""
+        """The tasks whose length the restraints, the blueprint, the ladder, the burial targets, the symmetric layout and the fold
+        references allow."""
         tasks = target_lengths(restrained_lengths(tasks, shape_constants(params)['restraints']), secstruct_constants(params)['ss_target'])
-        tasks = symmetric_lengths(ladder_lengths(tasks, sheet_constants(params)['ladder']), symmetry_constants(params))
+        tasks = burial_lengths(ladder_lengths(tasks, sheet_constants(params)['ladder']), burial_constants(params)['burial_targets'])
+        tasks = symmetric_lengths(tasks, symmetry_constants(params))
         return fold_lengths(tasks, fold_constants(params))
 
     def create_tasks(self, params):
@@ -870,6 +1018,7 @@ class GuidedRunner(UnconditionalRunner):
         c.update(shape_constants(params))
         c.update(secstruct_constants(params))
         c.update(sheet_constants(params))
+        c.update(burial_constants(params))
         c.update(symmetry_constants(params))
         c.update(binder_constants(params))
         c.update(fold_constants(params))
@@ -895,6 +1044,7 @@ class GuidedRunner(UnconditionalRunner):
             shape = shape_potential(constants, length, abar, device)
             secstruct = secstruct_potential(constants, length, abar, device)
             sheet = sheet_potential(constants, length, abar, device)
+            burial = burial_potential(constants, length, abar, device)
             symmetry = symmetry_potential(constants, length, abar, device)
             binder = binder_potential(constants, length, abar, device)
             fold = fold_potential(constants, length, abar, device)
@@ -905,7 +1055,7 @@ class GuidedRunner(UnconditionalRunner):
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
                     'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet,
-                                                        symmetry, binder, fold, diversity),
+                                                        burial, symmetry, binder, fold, diversity),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **chains, **self.partial_params(constants)})
@@ -921,6 +1071,9 @@ class GuidedRunner(UnconditionalRunner):
                 if constants['write_sheet'] and sheet is not None:
                     write_sheet_report(sampler.last_pairs, report_fields(sampler.last_shape, capi.SHEET_REPORT),
                                        os.path.join(outdir, 'sheet'), length, offset)
+                if constants['write_burial'] and burial is not None:
+                    write_burial_report(burial.burial_of(sampler.last_positions.to(burial.device)).cpu(), constants['burial_targets'],
+                                        report_fields(sampler.last_shape, capi.BURIAL_REPORT), os.path.join(outdir, 'burial'), length, offset)
                 if constants['write_symmetry'] and symmetry is not None:
                     write_symmetry_report(report_fields(sampler.last_shape, capi.SYMMETRY_REPORT), symmetry_header(symmetry),
                                           os.path.join(outdir, 'symmetry'), length, offset)
@@ -948,12 +1101,13 @@ class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
         if not (has_shape_terms(c) or has_secstruct_terms(c) or has_sheet_terms(c) or has_symmetry_terms(c) or has_binder_terms(c)
-                or has_fold_terms(c) or has_diversity_terms(c)):
+                or has_fold_terms(c) or has_diversity_terms(c) or has_burial_terms(c)):
             raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
                              'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target), a sheet term '
                              '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file), a binder term (--target_pdb '
                              'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance), a fold term (--template_pdb, --avoid_dir), '
-                             'a diversity term (--diversity_tm_max with --num_particles) or --symmetry')
+                             'a diversity term (--diversity_tm_max with --num_particles), a burial term (--burial_file, --bury with --bury_min, '
+                             '--expose with --expose_max, --burial_mean_min, --burial_mean_max) or --symmetry')
         return c
 
 
@@ -968,6 +1122,7 @@ def build_parser():
     add_binder_arguments(p)
     add_fold_arguments(p)
     add_diversity_arguments(p)
+    add_burial_arguments(p)
     return p
 
 

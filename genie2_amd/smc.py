@@ -1766,6 +1766,166 @@ class DiversityPotential(_HipPotential):
         return tuple(t for t in outs if t is not None)
 
 
+def load_burial_targets(path):
+    """A burial file -> [(i, lo, hi, weight), ...] for BurialPotential: one residue per line, `i lo hi [weight]`, residues 0-based
+    like the motif_locations files, lo and hi soft half-sphere counts, `inf` allowed for hi, weight 1 when omitted; `#` starts a
+    comment, blank lines are ignored.  A bad line raises ValueError('<path>:<line number>: ...')."""
+    out = []
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            fields = line.split('#', 1)[0].split()
+            if not fields:
+                continue
+            if len(fields) not in (3, 4):
+                raise ValueError('%s:%d: expected `i lo hi [weight]`, got %d fields' % (path, number, len(fields)))
+            try:
+                i = int(fields[0])
+                lo, hi = float(fields[1]), float(fields[2])
+                weight = float(fields[3]) if len(fields) == 4 else 1.0
+            except ValueError:
+                raise ValueError('%s:%d: the residue is an integer, lo, hi and weight numbers: %r' % (path, number, line.strip())) from None
+            out.append((i, lo, hi, weight))
+    return out
+
+
+def check_burial_targets(targets, n_res):
+    """The targets of BurialPotential, validated on the host: [(i, lo, hi, weight), ...] with i in 0..n_res-1, 0 <= lo <= hi (hi may
+    be inf), weight finite and >= 0 (1 when omitted), no residue listed twice; returned sorted by residue."""
+    import math
+    out, seen = [], set()
+    for k, t in enumerate(targets):
+        try:
+            t = tuple(t)
+        except TypeError:
+            raise ValueError('burial target %d: expected (i, lo, hi[, weight]), got %r' % (k, t)) from None
+        if len(t) not in (3, 4):
+            raise ValueError('burial target %d: expected (i, lo, hi[, weight]), got %r' % (k, t))
+        i = t[0]
+        if isinstance(i, bool) or not isinstance(i, numbers.Integral):
+            raise ValueError('burial target %d: the residue must be an integer, got %r' % (k, i))
+        try:
+            i, lo, hi, weight = int(i), float(t[1]), float(t[2]), float(t[3]) if len(t) == 4 else 1.0
+        except (TypeError, ValueError):
+            raise ValueError('burial target %d: lo, hi and weight must be numbers, got %r' % (k, t)) from None
+        if not 0 <= i < n_res:
+            raise ValueError('burial target %d: residue %d must lie in 0..%d' % (k, i, n_res - 1))
+        if not (0 <= lo <= hi) or math.isinf(lo):
+            raise ValueError('burial target %d: needs 0 <= lo <= hi with lo finite, got lo = %r, hi = %r' % (k, lo, hi))
+        if not (math.isfinite(weight) and weight >= 0):
+            raise ValueError('burial target %d: the weight must be finite and >= 0, got %r' % (k, weight))
+        if i in seen:
+            raise ValueError('burial target %d: residue %d is listed twice' % (k, i))
+        seen.add(i)
+        out.append((i, lo, hi, weight))
+    return sorted(out)
+
+
+def parse_residue_ranges(spec):
+    """'3,10-20,35' -> [3, 10, 11, ..., 20, 35]: 0-based residues and inclusive ranges, comma-separated, ascending, each once; a
+    ValueError for anything else (a reversed range, a residue named twice, a negative number, an empty item)."""
+    out = []
+    for item in str(spec).split(','):
+        item = item.strip()
+        ends = item.split('-')
+        if not 1 <= len(ends) <= 2 or not all(e.strip().isdigit() for e in ends):
+            raise ValueError('residue ranges look like 3,10-20,35 (0-based, inclusive), got %r' % (spec,))
+        first, last = int(ends[0]), int(ends[-1])
+        if last < first:
+            raise ValueError('the range %r runs backwards' % item)
+        out.extend(range(first, last + 1))
+    if len(set(out)) != len(out):
+        raise ValueError('a residue is named twice in %r' % (spec,))
+    return sorted(out)
+
+
+BURIAL_MAX_LENGTH = capi.BURIAL_MAX_LENGTH      # the longest chain whose staging fits in the kernel's 64 KiB of LDS (include/genie_hip.h)
+
+
+class BurialPotential(_HipPotential):
+    """Burial guidance as one HIP entry (genie_burial_potential, csrc/burial_kernels.hip; include/genie_hip.h states the mathematics):
+    `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside the other
+    built-in potentials (SumPotential adds them).  It is the one potential that tells inside from outside, by the half-sphere
+    exposure of a C-alpha chain (HSE-alpha).  In words:
+      the count         residue n points where its side chain would: along 2 x_n - x_{n-1} - x_{n+1}, made a unit vector with
+                        a floor of eps = 0.1 A on its length (the two ends have no direction).  Its burial c_n is the soft number
+                        of residues at least `separation` away in sequence that lie within `radius` of it (the binder potential's
+                        rational switch, 1/2 at `radius`) and on that side of it (a soft half-space of `width` Angstrom: 1/2 on the
+                        plane through the residue); an end counts half of its whole sphere.
+      targets           [(i, lo, hi[, weight]), ...], 0-based residues like the motif_locations files: c_i is kept in lo..hi by a
+                        squared hinge (hi may be inf: "bury"; lo may be 0: "expose"); load_burial_targets reads them from a file.
+      mean              (min, max): the mean of c_n over the chain is kept in that range by a squared hinge weighted mean_weight
+                        (max may be inf): a design with a core, not just a small one.
+    log p = -(E_targets + E_mean) / (2 var), var = xstart_variance(alphas_cumprod[step], tausq) computed on the device, so nothing on
+    the per-step path reads device memory from the host; the forward keeps the gradient the kernel computes and the backward scales
+    it.  The likelihood is unnormalised.
+
+    Everything is validated on the host (check_burial_targets) before the device is looked at; the per-residue table is built and
+    uploaded once.  A potential with no term enabled (no targets, and no mean or a mean_weight of 0) is a ValueError.  `describe(x)`
+    reports every sample of x with the names of capi.BURIAL_REPORT: 'burial_mean', 'burial_min', 'burial_max', 'n_burial_violated'
+    (targeted residues outside their range, int64), 'max_burial_violation', 'e_burial_target', 'e_burial_mean' (the weighted
+    energies, before the division by 2 var): [B] tensors on the potential's device.  `burial_of(x)` is [B, N], the c_n.
+
+    The defaults (radius 10 A, width 2 A, separation 3, eps 0.1 A, weights 1, tausq = 1 A^2) are design choices: no trained
+    checkpoint is in the tree, so their effect on sample quality is unmeasured.  Not built: tying targets to a motif's placement,
+    which moves per particle; chain breaks under --unit_chains (the direction stencil crosses them); a full-atom or C-beta model;
+    counting a binder target's atoms as neighbours."""
+
+    def __init__(self, n_res, alphas_cumprod, targets=None, mean=None, mean_weight=1.0, radius=10.0, width=2.0, separation=3, tausq=1.0,
+                 device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or not 1 <= n_res <= BURIAL_MAX_LENGTH:
+            raise ValueError('n_res must be an integer in 1..%d, got %r' % (BURIAL_MAX_LENGTH, n_res))
+        for name, v in (('radius', radius), ('width', width), ('tausq', tausq)):
+            if not (_is_scalar(v) and math.isfinite(float(v)) and float(v) > 0):
+                raise ValueError('%s must be finite and > 0, got %r' % (name, v))
+        if not (_is_scalar(mean_weight) and math.isfinite(float(mean_weight)) and float(mean_weight) >= 0):
+            raise ValueError('mean_weight must be finite and >= 0, got %r' % (mean_weight,))
+        if isinstance(separation, bool) or not isinstance(separation, numbers.Integral) or separation < 1:
+            raise ValueError('separation must be an integer >= 1, got %r' % (separation,))
+        if mean is not None:
+            try:
+                lo, hi = (float(v) for v in mean)
+            except (TypeError, ValueError):
+                raise ValueError('mean must be (min, max), got %r' % (mean,)) from None
+            if not (math.isfinite(lo) and lo >= 0 and hi >= lo):
+                raise ValueError('mean must be (min, max) with 0 <= min <= max, min finite, got %r' % (mean,))
+        self.targets = check_burial_targets(targets if targets is not None else [], int(n_res))
+        if not self.targets and (mean is None or float(mean_weight) == 0):
+            raise ValueError('no term enabled: give targets or mean (with a mean_weight above 0)')
+        # a term that is off is a weight of 0 (the mean) or no table (the targets) to the entry
+        self.mean, self.mean_weight = ((0.0, math.inf), 0.0) if mean is None else ((lo, hi), float(mean_weight))
+        self.radius, self.width, self.separation = float(radius), float(width), int(separation)
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.table = (None, None, None)
+        if self.targets:
+            rows = torch.zeros(3, self.n_res, dtype=torch.float32)
+            rows[1] = math.inf
+            for i, a, b, weight in self.targets:
+                rows[0, i], rows[1, i], rows[2, i] = a, b, weight
+            rows = rows.to(self.device)
+            self.table = (rows[0], rows[1], rows[2])
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, want='report')               # (the energies do not depend on var)
+        return _decode_report(report, capi.BURIAL_REPORT, capi.BURIAL_COUNTS)
+
+    def burial_of(self, x):
+        """[B, N] float32 on the potential's device: the soft half-sphere count c_n of every residue of every sample of x [B,N,3]."""
+        return self._launch(self._checked(x), self._one, want='burial')[0]
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous): (logp, grad), (report [B, 7],) or (burial_out [B, N],) as `want` says."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        outs = {'logp': lambda: [torch.empty(B, **f32), torch.empty_like(x), None, None],
+                'report': lambda: [None, None, torch.empty(B, len(capi.BURIAL_REPORT), **f32), None],
+                'burial': lambda: [None, None, None, torch.empty(B, self.n_res, **f32)]}[want]()
+        self._call('genie_burial_potential', self._stream(), B, self.n_res, _ptr(x), self.radius, self.width, self.separation,
+                   *(_ptr(t) for t in self.table), self.mean[0], self.mean[1], self.mean_weight, _ptr(var), *(_ptr(t) for t in outs),
+                   *self._workspace(self.lib.genie_burial_potential_work_bytes(B, self.n_res)))
+        return tuple(t for t in outs if t is not None)
+
+
 class SumPotential:
     """The sum of twisting functions: `SumPotential(a, b, ...)(x0, step) = a(x0, step) + b(x0, step) + ...`, added in that order.
     `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential); `describe` is the merge of the reports

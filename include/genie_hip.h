@@ -749,6 +749,69 @@ int genie_diversity_potential(genie_stream_t stream, int B, int K, int N, const 
                               float* tm_out /*[B,B] or NULL*/, void* work, size_t work_bytes);
 size_t genie_diversity_potential_work_bytes(int B, int K, int N);
 
+/* The burial potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle
+ * (csrc/burial_kernels.hip): which residues lie inside the design and which on its surface.  On a C-alpha model that is the
+ * half-sphere exposure (HSE-alpha): the number of C-alpha atoms in the half sphere that the virtual C-beta direction points into.
+ * Every other built-in potential is blind to inside and outside.  The reference has no counterpart.
+ * For particle b with C-alpha coordinates x_n, n = 0..N-1 (all N rows are used):
+ *   b_n   = 2 x_n - x_{n-1} - x_{n+1}  for 1 <= n <= N-2;  b_0 = b_{N-1} = 0          (the ends have no direction)
+ *   rho_n = sqrt(|b_n|^2 + eps^2),  u_n = b_n / rho_n          (eps = GENIE_BURIAL_EPS, 0.1 A: smooth where the chain is straight)
+ *   for every ordered pair n, j with |j - n| >= separation:
+ *     r = x_j - x_n,  q = |r|^2
+ *     s = 1 / (1 + (q / radius^2)^3)                 (genie_binder_potential's rational switch: from q, no square root, no exp)
+ *     h = u_n . r
+ *     g = 1/2 (1 + h / sqrt(h^2 + width^2))          (a soft half-space: 1/2 on the plane through x_n, -> 1 on the side-chain side)
+ *   c_n   = sum_j s g                                (the soft half-sphere count of residue n; ends: half the soft full-sphere count)
+ *   m     = (1/N) sum_n c_n
+ *   E_res  = sum_n w_n [ (lo_n - c_n)_+^2 + (c_n - hi_n)_+^2 ]        (per-residue table lo, hi, w [N]; hi may be +inf, w_n = 0: no target)
+ *   E_mean = mean_weight [ (mean_min - m)_+^2 + (m - mean_max)_+^2 ]  (mean_max may be +inf)
+ *   logp_out[b] = -(E_res + E_mean) / (2 var)
+ * grad_out[b,i] = d logp[b] / d x_i, analytic.  With k_n = w_n [(c_n - hi_n)_+ - (lo_n - c_n)_+] + (mean_weight / N) [(m - mean_max)_+
+ * - (mean_min - m)_+]:
+ *   f_nj = g ds/dr + s g' u_n,   ds/dr = -6 (q / radius^2)^2 s^2 r / radius^2,   g' = 1/2 width^2 / (h^2 + width^2)^(3/2)
+ *   a_n  = sum_j s g' r                                   (the pull on the direction u_n)
+ *   v_n  = (a_n - u_n (u_n . a_n)) / rho_n                (0 at the two ends)
+ *   grad[b,i] = -(1/var) [ sum_n k_n f_ni - k_i sum_j f_ij + 2 k_i v_i - k_{i-1} v_{i-1} - k_{i+1} v_{i+1} ]
+ * with k and v outside 0..N-1 taken as 0.  Nothing is divided by a distance: coincident residues, a straight chain (b_n = 0) and all
+ * residues in one point give finite outputs; the force of a pair with q / radius^2 >= 1e12 is taken as 0 (it is below 1e-48).  lo, hi
+ * and w are device arrays of N floats, given together or all NULL (no per-residue term); the caller validates them (0 <= lo <= hi,
+ * w >= 0 and finite).  `var` is one float in device memory; the likelihood is left unnormalised.  report_out[b] holds
+ * GENIE_BURIAL_REPORT floats:
+ *   burial_mean (m), burial_min, burial_max (the smallest and the largest c_n), n_burial_violated (residues with w_n > 0 and c_n
+ *   outside lo_n..hi_n), max_burial_violation (the largest (lo_n - c_n)_+ or (c_n - hi_n)_+ over the residues with w_n > 0),
+ *   e_burial_target (E_res), e_burial_mean (E_mean) (weighted, before the division by 2 var)
+ * (the count is stored as a float; the names differ from every other report's, so that a merged report keeps them all).  burial_out
+ * [B,N], optional, receives the c_n.  logp_out and grad_out are given together or both NULL; report_out and burial_out may be given
+ * alone; at least one output is asked for.
+ * Three launches on `stream`, the second only with grad_out.  Counts: grid (ceil(N / 64), B), 256 threads; every work-group stages
+ * the particle's x and u in dynamic LDS (24 N + 1024 bytes) and takes 64 centres n, one per lane; each wave walks a contiguous
+ * quarter of the neighbours j (wave-uniform: an LDS broadcast) in partial sums of 64, the four wave sums are added in wave order, and
+ * c_n goes to `work`.  Forces: the same grid; x, u, rho and k of the whole particle are staged (32 N + 10 240 bytes; every
+ * work-group forms m from the c_n in one fixed order), lane i walks the pairs again, once as the centre (a_i and sum_j f_ij) and once
+ * as the neighbour of centre j (k_j f_ji, skipped where k_j = 0), and stores sum_n k_n f_ni - k_i sum_j f_ij and k_i v_i, 6 floats.
+ * Stencil: grid (ceil(N / 256), B), 256 threads, one residue per thread: the three-residue sum above; work-group 0 of the particle
+ * reduces the c_n in a fixed order and writes logp and the report.  `work` holds 7 N floats per particle
+ * (genie_burial_potential_work_bytes(B, N) = 28 B N bytes, 4-byte aligned; 0 for sizes this entry refuses).  No allocation, no
+ * synchronisation, no host read, no atomics, no scatter: every output is written once in a fixed order, so two calls on the same
+ * inputs are bitwise equal.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 1 or above GENIE_BURIAL_MAX_LENGTH (1728: the forces' staging fills the 64 KiB of LDS a kernel gets without asking); x0
+ * or var NULL; separation < 1; radius or width not finite or <= 0 (or radius^2 no normal float); one or two of lo, hi, w given; a
+ * negative or non-finite mean_weight, mean_min or mean_max (mean_max alone may be +inf); mean_max below mean_min; logp_out asked for
+ * with no term enabled (no table and mean_weight 0); no output asked for; logp_out and grad_out not given together; `work` NULL,
+ * misaligned or work_bytes too small. */
+#define GENIE_BURIAL_REPORT 7   /* burial_mean, burial_min, burial_max, n_burial_violated, max_burial_violation, e_burial_target,
+                                   e_burial_mean */
+#define GENIE_BURIAL_EPS 0.1f
+#define GENIE_BURIAL_MAX_LENGTH 1728
+int genie_burial_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, float radius, float width, int separation,
+                           const float* lo, const float* hi, const float* w /*[N] each, device; all three NULL: no per-residue term*/,
+                           float mean_min, float mean_max, float mean_weight, const float* var /*[1], device*/,
+                           float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                           float* report_out /*[B,GENIE_BURIAL_REPORT] or NULL*/, float* burial_out /*[B,N] or NULL: the c_n*/,
+                           void* work, size_t work_bytes);
+size_t genie_burial_potential_work_bytes(int B, int N);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
