@@ -138,6 +138,9 @@ SYMBOLS = {
     'genie_burial_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 3 +
                                [C.c_float] * 3 + [C.c_void_p] * 6 + [C.c_size_t]),
     'genie_burial_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'genie_envelope_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 5 +
+                                 [C.c_void_p] * 7 + [C.c_size_t]),
+    'genie_envelope_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -178,6 +181,11 @@ BURIAL_REPORT = ('burial_mean', 'burial_min', 'burial_max', 'n_burial_violated',
                  'e_burial_mean')      # GENIE_BURIAL_REPORT slots
 BURIAL_COUNTS = ('n_burial_violated',)
 BURIAL_MAX_LENGTH = 1728        # GENIE_BURIAL_MAX_LENGTH
+ENVELOPE_REPORT = ('n_outside', 'max_outside', 'n_uncovered', 'max_uncovered', 'e_envelope_inside', 'e_envelope_cover')      # GENIE_ENVELOPE_REPORT slots
+ENVELOPE_COUNTS = ('n_outside', 'n_uncovered')
+ENVELOPE_EPS, ENVELOPE_CHUNK = 0.1, 1024        # GENIE_ENVELOPE_EPS, GENIE_ENVELOPE_CHUNK: the rows of the walked side staged in LDS at a time
+ENVELOPE_FILL = 2048        # GENIE_ENVELOPE_FILL: work-groups of a launch from which it runs 4 waves per work-group instead of 16
+ENVELOPE_MAX_LENGTH, ENVELOPE_MAX_POINTS = 4096, 16384      # GENIE_ENVELOPE_MAX_LENGTH, _MAX_POINTS
 TMALIGN_NORMS = ('query', 'reference', 'shorter', 'longer')      # norm 0..3 of genie_tm_align and genie_fold_align_potential
 
 _lib = None

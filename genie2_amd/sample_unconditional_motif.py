@@ -64,12 +64,18 @@ is within one device batch only: across batches and runs use `--avoid_dir`.
 `--burial_weight`, `--burial_mean_weight`, `--burial_radius`, `--burial_width`, `--burial_separation`, `--burial_tausq` and
 `--write_burial`: the flags of add_burial_arguments in the same module) add burial guidance by half-sphere exposure, summed after the
 sheet term and before symmetry; `--write_burial` writes outdir/burial/{length}_{index}.txt as that CLI does.  The listed residues are
-positions of the design, not of the motif: a motif's placement moves per particle and the targets do not follow it."""
+positions of the design, not of the motif: a motif's placement moves per particle and the targets do not follow it.
+
+`--envelope_shape SPEC` or `--envelope_file FILE` (with `--envelope_spacing`, `--envelope_keep_frame`, `--envelope_inside_distance`,
+`--envelope_inside_weight`, `--envelope_cover_distance`, `--envelope_cover_weight`, `--envelope_softness`, `--envelope_tausq` and
+`--write_envelope`: the flags of add_envelope_arguments in the same module) add envelope guidance -- the design stays inside a given 3D
+shape and fills it -- summed after burial and before symmetry; `--write_envelope` writes outdir/envelope/ as that CLI does.  The
+envelope does not follow the motif's placement either."""
 import os
 
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_burial_arguments, add_diversity_arguments, add_fold_arguments, add_guidance_arguments,
+from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_burial_arguments, add_diversity_arguments, add_envelope_arguments, add_fold_arguments, add_guidance_arguments,
                                          add_secstruct_arguments, add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
 
 
@@ -171,6 +177,7 @@ def build_parser():
     add_fold_arguments(p)
     add_diversity_arguments(p)
     add_burial_arguments(p)
+    add_envelope_arguments(p)
     return p
 
 

@@ -2,8 +2,8 @@
 unconditional CLI's flags and output layout, outdir/pdbs/{length}_{index}.pdb, with every batch guided by a ShapePotential
 (genie2_amd/smc.py, csrc/shape_kernels.hip): `--rog_max` caps the radius of gyration, `--clash_distance` penalises C-alpha pairs
 closer than that (residues at least `--clash_separation` apart), `--restraint_file` keeps pairwise distances in given ranges.  At
-least one of the three, or a secondary-structure, sheet, symmetry, binder, fold or diversity term (below), or a burial term (below),
-is needed.
+least one of the three, or a secondary-structure, sheet, symmetry, binder, fold or diversity term (below), or a burial or an envelope
+term (below), is needed.
 
 The restraint file has one restraint per line, `i j lo hi [weight]`: residues 0-based like the motif_locations files, distances in
 Angstrom, `inf` allowed for hi, weight 1 when omitted; `#` starts a comment.  A length too short for a restrained residue is skipped.
@@ -100,10 +100,26 @@ written structure (its count, and the range asked of it or `- -`), then one `key
 Not built: tying targets to a motif's placement, chain breaks under `--unit_chains` (the direction stencil crosses them), a full-atom
 or C-beta model, counting a binder target's atoms as neighbours.
 
+`--envelope_shape SPEC` or `--envelope_file FILE` (exactly one) says what shape the design should have: an EnvelopePotential
+(csrc/envelope_kernels.hip) keeps every residue within `--envelope_inside_distance` (default 3 A, weight `--envelope_inside_weight`) of
+the envelope's points and every point within `--envelope_cover_distance` (default 5 A, weight `--envelope_cover_weight`) of the design,
+both as soft minima of softness `--envelope_softness` (default 4 A^2), so that the design stays inside the shape and fills it; a weight
+of 0 switches a term off.  SPEC is `sphere:R`, `ellipsoid:A,B,C`, `cylinder:R,L`, `torus:R,r` (axis z) or `box:A,B,C` (full edge
+lengths) in Angstrom, filled with lattice points `--envelope_spacing` (default 3 A) apart; FILE is a `.pdb` (every ATOM / HETATM record:
+a C-alpha trace, a full-atom model, the pseudo-atoms a map tool writes) or text lines `x y z [weight]`, `#` starting a comment.  The
+envelope's weighted centroid is moved to the origin, where designs are born; `--envelope_keep_frame` leaves it where it is (with
+`--target_pdb`).  `--envelope_tausq` is the likelihood variance.  The term is summed after burial and before symmetry, and is enough
+on its own.  Both sources at once and an envelope flag without either end the run.  `--write_envelope` adds
+outdir/envelope/{length}_{index}.txt: a line `residue I A` per residue of the written structure (its soft distance to the envelope),
+`covered_fraction F` (the weight share of points within the cover distance), then one `key value` line per field of
+EnvelopePotential.describe; and once outdir/envelope/envelope.pdb, the points as placed, as HETATM pseudo-atoms.  Not built: rotating
+or fitting the envelope to the design, assigning regions of it to residues, envelopes that follow a motif's placement, density-map
+file formats.
+
 `--num_particles`, `--num_steps`, `--guidance_alpha`, `--ess_threshold`, `--last_unguided_steps`, `--input_pdb` / `--start_step` /
 `--write_start_rmsd` and `--resume` are those of the motif CLI (genie2_amd/sample_unconditional_motif.py), which takes the flags of
 add_shape_arguments, add_secstruct_arguments, add_sheet_arguments, add_symmetry_arguments, add_binder_arguments, add_fold_arguments and
-add_diversity_arguments and add_burial_arguments too and then guides
+add_diversity_arguments, add_burial_arguments and add_envelope_arguments too and then guides
 with the sum of the potentials asked for."""
 import os
 
@@ -953,6 +969,125 @@ def write_burial_report(burial, targets, report, directory, length, offset):
     write_report(report, BURIAL_COUNTS, directory, length, offset, heads)
 
 
+ENVELOPE_DEFAULTS = dict(envelope_file=None, envelope_shape=None, envelope_spacing=3.0, envelope_keep_frame=False,
+                         envelope_inside_distance=3.0, envelope_inside_weight=1.0, envelope_cover_distance=5.0, envelope_cover_weight=1.0,
+                         envelope_softness=4.0, envelope_tausq=1.0, write_envelope=False)
+ENVELOPE_EPS, ENVELOPE_MAX_POINTS = 0.1, 16384      # capi.ENVELOPE_EPS, capi.ENVELOPE_MAX_POINTS
+
+
+def add_envelope_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --rog_max)'
+    parser.add_argument('--envelope_file', type=str, default=None,
+                        help='Guide the design to stay inside and to fill the shape these points outline: a .pdb (every ATOM / HETATM '
+                             'record) or text lines `x y z [weight]`; default: no such term' + tail)
+    parser.add_argument('--envelope_shape', type=str, default=None,
+                        help='The same with a solid: sphere:R, ellipsoid:A,B,C, cylinder:R,L, torus:R,r (axis z) or box:A,B,C (full edge '
+                             'lengths), in Angstrom, filled with lattice points --envelope_spacing apart' + tail)
+    parser.add_argument('--envelope_spacing', type=float, default=3.0, help='Lattice spacing of --envelope_shape in Angstrom' + tail)
+    parser.add_argument('--envelope_keep_frame', action='store_true',
+                        help='Leave the envelope where its coordinates put it (with --target_pdb, say); default: its weighted centroid is '
+                             'moved to the origin, where designs are born' + tail)
+    parser.add_argument('--envelope_inside_distance', type=float, default=3.0,
+                        help='Soft distance in Angstrom from the nearest envelope points a residue may have' + tail)
+    parser.add_argument('--envelope_inside_weight', type=float, default=1.0, help='Weight of the stay-inside term; 0: off' + tail)
+    parser.add_argument('--envelope_cover_distance', type=float, default=5.0,
+                        help='Soft distance in Angstrom from the nearest residues an envelope point may have' + tail)
+    parser.add_argument('--envelope_cover_weight', type=float, default=1.0, help='Weight of the fill-it term; 0: off' + tail)
+    parser.add_argument('--envelope_softness', type=float, default=4.0, help='Softness tau of the two soft minima, Angstrom^2' + tail)
+    parser.add_argument('--envelope_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the envelope terms' + tail)
+    parser.add_argument('--write_envelope', action='store_true',
+                        help='Write outdir/envelope/{length}_{index}.txt: the soft distance of every residue of every written structure '
+                             'to the envelope, the covered fraction, then counts, worst excesses and energies; and once '
+                             'outdir/envelope/envelope.pdb, the points as placed' + tail)
+
+
+def envelope_constants(params):
+    """The envelope keys of a runner's constants: the flags of add_envelope_arguments; with --envelope_file or --envelope_shape also
+    'envelope', the points read or generated and ready to travel to a worker process: 'points' float64 numpy [M, 3] as the file or the
+    solid gives them (EnvelopePotential centres them unless --envelope_keep_frame) and 'weights' float64 numpy [M] or None.  Both
+    sources at once, an envelope flag without either, a value out of range, both weights 0 and a file or a specification that does not
+    hold up end the run here."""
+    import math
+    from .smc import envelope_shape_points, load_envelope
+    c = {k: params.get(k, v) for k, v in ENVELOPE_DEFAULTS.items()}
+    c['write_envelope'], c['envelope_keep_frame'] = bool(c['write_envelope']), bool(c['envelope_keep_frame'])
+    c['envelope'] = None
+    if c['envelope_file'] is None and c['envelope_shape'] is None:
+        given = [k for k, v in ENVELOPE_DEFAULTS.items() if c[k] != v]
+        if given:
+            raise SystemExit('%s: an envelope flag needs a term: --envelope_file or --envelope_shape' % ', '.join('--' + k for k in given))
+        return c
+    if c['envelope_file'] is not None and c['envelope_shape'] is not None:
+        raise SystemExit('--envelope_file and --envelope_shape both name the envelope: give one of them')
+    for k in ('envelope_inside_distance', 'envelope_cover_distance'):
+        if not (math.isfinite(c[k]) and c[k] > ENVELOPE_EPS):
+            raise SystemExit('--%s must be finite and above %g, got %r' % (k, ENVELOPE_EPS, c[k]))
+    for k in ('envelope_inside_weight', 'envelope_cover_weight'):
+        if not (math.isfinite(c[k]) and c[k] >= 0):
+            raise SystemExit('--%s must be finite and >= 0, got %r' % (k, c[k]))
+    for k in ('envelope_spacing', 'envelope_softness', 'envelope_tausq'):
+        if not (math.isfinite(c[k]) and c[k] > 0):
+            raise SystemExit('--%s must be finite and > 0, got %r' % (k, c[k]))
+    if c['envelope_inside_weight'] == 0 and c['envelope_cover_weight'] == 0:
+        raise SystemExit('--envelope_inside_weight and --envelope_cover_weight are both 0: nothing to guide')
+    try:
+        if c['envelope_file'] is not None:
+            points, weights = load_envelope(c['envelope_file'])
+            if len(points) > ENVELOPE_MAX_POINTS:
+                raise ValueError('%s has %d points, at most %d fit' % (c['envelope_file'], len(points), ENVELOPE_MAX_POINTS))
+            if not bool((weights > 0).all()) or not bool((weights < math.inf).all()):
+                raise ValueError('%s: every weight must be finite and > 0' % c['envelope_file'])
+            weights = None if bool((weights == 1).all()) else weights.numpy()
+        else:
+            points, weights = envelope_shape_points(c['envelope_shape'], c['envelope_spacing']), None
+    except (OSError, ValueError) as e:
+        raise SystemExit('--envelope_file / --envelope_shape: %s' % e) from None
+    c['envelope'] = dict(points=points.numpy(), weights=weights)
+    return c
+
+
+def has_envelope_terms(constants):
+    return constants.get('envelope') is not None
+
+
+def envelope_potential(constants, length, abar, device):
+    """The EnvelopePotential the constants ask for at this length, or None when they name no envelope."""
+    if not has_envelope_terms(constants):
+        return None
+    from .smc import EnvelopePotential
+    e = constants['envelope']
+    return EnvelopePotential(length, abar, e['points'], weights=e['weights'], inside_distance=constants['envelope_inside_distance'],
+                             inside_weight=constants['envelope_inside_weight'], cover_distance=constants['envelope_cover_distance'],
+                             cover_weight=constants['envelope_cover_weight'], softness=constants['envelope_softness'],
+                             tausq=constants['envelope_tausq'], center=not constants['envelope_keep_frame'], device=device)
+
+
+def write_envelope_report(distance, gap, weights, cover_distance, report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a line `residue I A` per residue (row i of `distance` [rows, N],
+    EnvelopePotential.distance_of of TwistedSampler.last_positions, %.3f), then `covered_fraction F`, the weight share of the envelope
+    points whose soft distance to the design (row i of `gap` [rows, M], gap_of) is at most `cover_distance` (`weights` [M] or None:
+    all 1), then a `key value` line per field of `report` (the envelope fields of last_shape), %.3f for Angstrom and energies, %d for
+    counts."""
+    from .capi import ENVELOPE_COUNTS
+    covered = (gap <= cover_distance).double()
+    share = covered.mean(dim=1) if weights is None else (covered * weights.double()[None]).sum(dim=1) / weights.double().sum()
+    heads = ['\n'.join(['residue {} {:.3f}'.format(n, v) for n, v in enumerate(row)] + ['covered_fraction {:.3f}'.format(f)])
+             for row, f in zip(distance.tolist(), share.tolist())]
+    write_report(report, ENVELOPE_COUNTS, directory, length, offset, heads)
+
+
+def write_envelope_pdb(points, weights, path):
+    """The envelope as placed, [M, 3] with weights [M] or None, as HETATM pseudo-atoms (the weight in the occupancy column), so that a
+    viewer shows design and envelope together; residue numbers wrap at 10000."""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, 'w') as fh:
+        for m, (x, y, z) in enumerate(points.tolist()):
+            w = 1.0 if weights is None else float(weights[m])
+            fh.write('HETATM{:5d}  C   ENV E{:4d}    {:8.3f}{:8.3f}{:8.3f}{:6.2f}{:6.2f}           C\n'.format((m + 1) % 100000, (m + 1) % 10000,
+                                                                                                             x, y, z, w, 0.0))
+        fh.write('END\n')
+
+
 def sum_potentials(*potentials):
     """The potentials that are not None, in that order: the one there is, their SumPotential, or None."""
     from .smc import SumPotential
@@ -997,7 +1132,7 @@ def add_guidance_arguments(parser, tail, *names):
 
 class GuidedRunner(UnconditionalRunner):
     """The runner of the guided CLIs: every batch sampled by a TwistedSampler under the sum of the potentials of `batch_potentials`
-    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, burial, symmetry, binder, fold and diversity
+    (a subclass's own, made per batch; none here) and the shape, secondary-structure, sheet, burial, envelope, symmetry, binder, fold and diversity
     potentials the constants ask for, in that order; `after_batch` writes a subclass's own reports.  With --unit_chains the features hold the units as chains."""
 
     def guided_lengths(self, tasks, params):
@@ -1019,6 +1154,7 @@ class GuidedRunner(UnconditionalRunner):
         c.update(secstruct_constants(params))
         c.update(sheet_constants(params))
         c.update(burial_constants(params))
+        c.update(envelope_constants(params))
         c.update(symmetry_constants(params))
         c.update(binder_constants(params))
         c.update(fold_constants(params))
@@ -1045,6 +1181,10 @@ class GuidedRunner(UnconditionalRunner):
             secstruct = secstruct_potential(constants, length, abar, device)
             sheet = sheet_potential(constants, length, abar, device)
             burial = burial_potential(constants, length, abar, device)
+            envelope = envelope_potential(constants, length, abar, device)
+            if constants['write_envelope'] and envelope is not None and not os.path.exists(os.path.join(outdir, 'envelope', 'envelope.pdb')):
+                write_envelope_pdb(envelope.points.cpu(), None if envelope.weights is None else envelope.weights.cpu(),
+                                   os.path.join(outdir, 'envelope', 'envelope.pdb'))
             symmetry = symmetry_potential(constants, length, abar, device)
             binder = binder_potential(constants, length, abar, device)
             fold = fold_potential(constants, length, abar, device)
@@ -1055,7 +1195,7 @@ class GuidedRunner(UnconditionalRunner):
                     'length': length, 'scale': constants['scale'], 'num_samples': batch,
                     'outdir': outdir, 'prefix': str(length), 'offset': offset,
                     'twisting_function': sum_potentials(*self.batch_potentials(constants, length, abar, device), shape, secstruct, sheet,
-                                                        burial, symmetry, binder, fold, diversity),
+                                                        burial, envelope, symmetry, binder, fold, diversity),
                     'guidance_alpha': constants['guidance_alpha'],
                     'ess_threshold': constants['ess_threshold'], 'last_unguided_steps': constants['last_unguided_steps'],
                     'num_steps': constants.get('num_steps'), **systems, **chains, **self.partial_params(constants)})
@@ -1074,6 +1214,11 @@ class GuidedRunner(UnconditionalRunner):
                 if constants['write_burial'] and burial is not None:
                     write_burial_report(burial.burial_of(sampler.last_positions.to(burial.device)).cpu(), constants['burial_targets'],
                                         report_fields(sampler.last_shape, capi.BURIAL_REPORT), os.path.join(outdir, 'burial'), length, offset)
+                if constants['write_envelope'] and envelope is not None:
+                    at = sampler.last_positions.to(envelope.device)
+                    write_envelope_report(envelope.distance_of(at).cpu(), envelope.gap_of(at).cpu(),
+                                          None if envelope.weights is None else envelope.weights.cpu(), envelope.cover_distance,
+                                          report_fields(sampler.last_shape, capi.ENVELOPE_REPORT), os.path.join(outdir, 'envelope'), length, offset)
                 if constants['write_symmetry'] and symmetry is not None:
                     write_symmetry_report(report_fields(sampler.last_shape, capi.SYMMETRY_REPORT), symmetry_header(symmetry),
                                           os.path.join(outdir, 'symmetry'), length, offset)
@@ -1101,13 +1246,14 @@ class ShapeRunner(GuidedRunner):
     def create_constants(self, params):
         c = super().create_constants(params)
         if not (has_shape_terms(c) or has_secstruct_terms(c) or has_sheet_terms(c) or has_symmetry_terms(c) or has_binder_terms(c)
-                or has_fold_terms(c) or has_diversity_terms(c) or has_burial_terms(c)):
+                or has_fold_terms(c) or has_diversity_terms(c) or has_burial_terms(c) or has_envelope_terms(c)):
             raise SystemExit('no shape term asked for: give --rog_max, --clash_distance or --restraint_file, a secondary-structure '
                              'term (--helix_min, --helix_max, --extended_min, --extended_max, --ss_target), a sheet term '
                              '(--antiparallel_min, --antiparallel_max, --parallel_min, --parallel_max, --ladder_file), a binder term (--target_pdb '
                              'with --hotspots, --contacts_min, --contacts_max or --target_clash_distance), a fold term (--template_pdb, --avoid_dir), '
                              'a diversity term (--diversity_tm_max with --num_particles), a burial term (--burial_file, --bury with --bury_min, '
-                             '--expose with --expose_max, --burial_mean_min, --burial_mean_max) or --symmetry')
+                             '--expose with --expose_max, --burial_mean_min, --burial_mean_max), an envelope term (--envelope_file, --envelope_shape) '
+                             'or --symmetry')
         return c
 
 
@@ -1123,6 +1269,7 @@ def build_parser():
     add_fold_arguments(p)
     add_diversity_arguments(p)
     add_burial_arguments(p)
+    add_envelope_arguments(p)
     return p
 
 

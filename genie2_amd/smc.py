@@ -1926,6 +1926,196 @@ class BurialPotential(_HipPotential):
         return tuple(t for t in outs if t is not None)
 
 
+ENVELOPE_MAX_LENGTH, ENVELOPE_MAX_POINTS = capi.ENVELOPE_MAX_LENGTH, capi.ENVELOPE_MAX_POINTS      # include/genie_hip.h says what sets them
+
+
+def load_envelope(path):
+    """An envelope file -> (points [M, 3], weights [M]) float64 tensors for EnvelopePotential.  A `.pdb` file gives the coordinates of
+    every ATOM / HETATM record (columns 31-54), weights 1: a C-alpha trace, a full-atom model and a pseudo-atom file from a map tool
+    all work.  Any other file is text, one point per line, `x y z [weight]` in Angstrom, weight 1 when omitted; `#` starts a comment,
+    blank lines are ignored.  A bad line raises ValueError('<path>:<line number>: ...'), a file without a point ValueError('<path>:
+    ...')."""
+    points, weights = [], []
+    pdb = str(path).lower().endswith('.pdb')
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            if pdb:
+                if not line.startswith(('ATOM', 'HETATM')):
+                    continue
+                try:
+                    row = [float(line[30:38]), float(line[38:46]), float(line[46:54]), 1.0]
+                except ValueError:
+                    raise ValueError('%s:%d: no coordinates in columns 31-54: %r' % (path, number, line.rstrip())) from None
+            else:
+                fields = line.split('#', 1)[0].split()
+                if not fields:
+                    continue
+                if len(fields) not in (3, 4):
+                    raise ValueError('%s:%d: expected `x y z [weight]`, got %d fields' % (path, number, len(fields)))
+                try:
+                    row = [float(f) for f in fields] + [1.0] * (4 - len(fields))
+                except ValueError:
+                    raise ValueError('%s:%d: x, y, z and weight are numbers: %r' % (path, number, line.strip())) from None
+            points.append(row[:3])
+            weights.append(row[3])
+    if not points:
+        raise ValueError('%s: no envelope point (%s)' % (path, 'no ATOM or HETATM record' if pdb else 'no `x y z [weight]` line'))
+    return torch.tensor(points, dtype=torch.float64), torch.tensor(weights, dtype=torch.float64)
+
+
+ENVELOPE_SHAPES = {'sphere': ('R',), 'ellipsoid': ('A', 'B', 'C'), 'cylinder': ('R', 'L'), 'torus': ('R', 'r'), 'box': ('A', 'B', 'C')}
+
+
+def envelope_shape_points(spec, spacing):
+    """The points of a solid for EnvelopePotential, [M, 3] float64, centred on the origin: `sphere:R`, `ellipsoid:A,B,C` (semi-axes
+    along x, y, z), `cylinder:R,L` (radius and full length, axis z), `torus:R,r` (ring radius and tube radius, axis z) and `box:A,B,C`
+    (full edge lengths), in Angstrom.  They are the points (i, j, k) spacing of the integer lattice, the origin included, that satisfy
+    the solid's closed inequality, in ascending (i, j, k) order: deterministic, host only.  A ValueError for a specification that does
+    not parse, a size or spacing that is not finite and positive, a solid that holds no lattice point (a torus may miss them all) and
+    one with more than ENVELOPE_MAX_POINTS points (use a larger spacing)."""
+    import math
+    name, _, tail = str(spec).partition(':')
+    name = name.strip().lower()
+    if name not in ENVELOPE_SHAPES:
+        raise ValueError('an envelope shape is one of %s, got %r' % (', '.join('%s:%s' % (k, ','.join(v)) for k, v in ENVELOPE_SHAPES.items()), spec))
+    try:
+        sizes = [float(v) for v in tail.split(',')]
+    except ValueError:
+        sizes = []
+    if len(sizes) != len(ENVELOPE_SHAPES[name]) or not all(math.isfinite(v) and v > 0 for v in sizes):
+        raise ValueError('%s takes %d finite sizes above 0, %s:%s, got %r' % (name, len(ENVELOPE_SHAPES[name]), name, ','.join(ENVELOPE_SHAPES[name]), spec))
+    if not (_is_scalar(spacing) and math.isfinite(float(spacing)) and float(spacing) > 0):
+        raise ValueError('spacing must be finite and > 0, got %r' % (spacing,))
+    h = float(spacing)
+    if name == 'sphere':
+        sizes = sizes * 3
+    if name in ('sphere', 'ellipsoid'):
+        half = sizes
+        inside = lambda x, y, z: (x / sizes[0]) ** 2 + (y / sizes[1]) ** 2 + (z / sizes[2]) ** 2 <= 1.0      # noqa: E731
+    elif name == 'cylinder':
+        half = [sizes[0], sizes[0], sizes[1] / 2]
+        inside = lambda x, y, z: (x * x + y * y <= sizes[0] ** 2) & (z.abs() <= sizes[1] / 2)      # noqa: E731
+    elif name == 'torus':
+        half = [sizes[0] + sizes[1], sizes[0] + sizes[1], sizes[1]]
+        inside = lambda x, y, z: (torch.sqrt(x * x + y * y) - sizes[0]) ** 2 + z * z <= sizes[1] ** 2      # noqa: E731
+    else:
+        half = [v / 2 for v in sizes]
+        inside = lambda x, y, z: (x.abs() <= sizes[0] / 2) & (y.abs() <= sizes[1] / 2) & (z.abs() <= sizes[2] / 2)      # noqa: E731
+    reach = [int(math.floor(v / h)) for v in half]
+    cells = 1
+    for r in reach:
+        cells *= 2 * r + 1
+    if cells > 64 * ENVELOPE_MAX_POINTS:                                # (the bounding box alone says so, before anything is allocated)
+        raise ValueError('%s at spacing %g has more than %d points: use a larger spacing' % (spec, h, ENVELOPE_MAX_POINTS))
+    axes = [torch.arange(-r, r + 1, dtype=torch.float64) * h for r in reach]
+    x, y, z = torch.meshgrid(*axes, indexing='ij')                      # ascending (i, j, k): k fastest
+    pts = torch.stack([x, y, z], dim=-1)[inside(x, y, z)]
+    if len(pts) == 0:
+        raise ValueError('%s at spacing %g holds no lattice point: use a smaller spacing' % (spec, h))
+    if len(pts) > ENVELOPE_MAX_POINTS:
+        raise ValueError('%s at spacing %g has %d points, more than %d: use a larger spacing' % (spec, h, len(pts), ENVELOPE_MAX_POINTS))
+    return pts
+
+
+class EnvelopePotential(_HipPotential):
+    """Envelope guidance as one HIP entry (genie_envelope_potential, csrc/envelope_kernels.hip; include/genie_hip.h states the
+    mathematics): `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside
+    the other built-in potentials (SumPotential adds them).  It is the one potential that says what shape the design should have:
+    `points` [M, 3] with `weights` [M] (None: all 1) are the envelope -- the lattice points of a solid (envelope_shape_points), the
+    atoms of an existing protein or the pseudo-atoms of a low-resolution map (load_envelope) -- in the frame the sampler works in.
+    Designs are born around the origin, so with `center` (the default) the envelope's weighted centroid is moved there; center=False
+    keeps the frame of the points (with a binder target, say).  Two terms, each a squared hinge over a soft minimum of squared
+    distances with softness `softness` (tau, A^2):
+      stay inside      every residue's soft distance a_n to the nearest points is kept at or below inside_distance (weight
+                       inside_weight);
+      fill it          every point's soft distance c_m to the nearest residues is kept at or below cover_distance (weight
+                       cover_weight, times N / sum v so that the two terms stay comparable at any point count).
+    A weight of 0 switches a term off; both 0 is a ValueError.  log p = -(E_inside + E_cover) / (2 var), var =
+    xstart_variance(alphas_cumprod[step], tausq) computed on the device, so nothing on the per-step path reads device memory from the
+    host; the forward keeps the gradient the kernel computes and the backward scales it.  The likelihood is unnormalised.
+
+    Everything is validated on the host before the device is looked at; points and weights are uploaded once (`points`, `weights` as
+    placed).  `describe(x)` reports every sample of x with the names of capi.ENVELOPE_REPORT: 'n_outside', 'n_uncovered' (int64),
+    'max_outside', 'max_uncovered' (Angstrom beyond the two distances), 'e_envelope_inside', 'e_envelope_cover' (the weighted
+    energies, before the division by 2 var): [B] tensors on the potential's device.  `distance_of(x)` is [B, N], the a_n;
+    `gap_of(x)` is [B, M], the c_m.
+
+    The defaults (inside 3 A, cover 5 A, softness 4 A^2, weights 1, tausq = 1 A^2) are design choices: no trained checkpoint is in
+    the tree, so their effect on sample quality is unmeasured.  Not built: rotating or fitting the envelope to the design, assigning
+    regions of it to residues, envelopes that follow a motif's placement, density-map file formats."""
+
+    def __init__(self, n_res, alphas_cumprod, points, weights=None, inside_distance=3.0, inside_weight=1.0, cover_distance=5.0,
+                 cover_weight=1.0, softness=4.0, tausq=1.0, center=True, device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or not 1 <= n_res <= ENVELOPE_MAX_LENGTH:
+            raise ValueError('n_res must be an integer in 1..%d, got %r' % (ENVELOPE_MAX_LENGTH, n_res))
+        try:
+            y = torch.as_tensor(points).detach().to(dtype=torch.float64, device='cpu')
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('points must be [M, 3] coordinates, got %r' % (type(points),)) from None
+        if y.dim() != 2 or y.shape[1] != 3 or not 1 <= y.shape[0] <= ENVELOPE_MAX_POINTS:
+            raise ValueError('points must be [M, 3] with M in 1..%d, got %s' % (ENVELOPE_MAX_POINTS, tuple(y.shape)))
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError('points has a coordinate that is not finite')
+        v = None
+        if weights is not None:
+            try:
+                v = torch.as_tensor(weights).detach().to(dtype=torch.float64, device='cpu')
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError('weights must be [M] numbers, got %r' % (type(weights),)) from None
+            if tuple(v.shape) != (y.shape[0],):
+                raise ValueError('weights must be [%d], one per point, got %s' % (y.shape[0], tuple(v.shape)))
+            if not bool((torch.isfinite(v) & (v > 0)).all()):
+                raise ValueError('every weight must be finite and > 0')
+        for name, d in (('inside_distance', inside_distance), ('cover_distance', cover_distance)):
+            if not (_is_scalar(d) and math.isfinite(float(d)) and float(d) > capi.ENVELOPE_EPS):
+                raise ValueError('%s must be finite and above eps = %g A, got %r' % (name, capi.ENVELOPE_EPS, d))
+        for name, d in (('inside_weight', inside_weight), ('cover_weight', cover_weight)):
+            if not (_is_scalar(d) and math.isfinite(float(d)) and float(d) >= 0):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, d))
+        for name, d in (('softness', softness), ('tausq', tausq)):
+            if not (_is_scalar(d) and math.isfinite(float(d)) and float(d) > 0):
+                raise ValueError('%s must be finite and > 0, got %r' % (name, d))
+        if float(inside_weight) == 0 and float(cover_weight) == 0:
+            raise ValueError('no term enabled: inside_weight and cover_weight are both 0')
+        if center:
+            u = torch.ones(len(y), dtype=torch.float64) if v is None else v
+            y = y - (u[:, None] * y).sum(dim=0, keepdim=True) / u.sum()
+        self.inside_distance, self.inside_weight = float(inside_distance), float(inside_weight)
+        self.cover_distance, self.cover_weight = float(cover_distance), float(cover_weight)
+        self.softness, self.center = float(softness), bool(center)
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        self.M = int(y.shape[0])
+        self.points = y.to(torch.float32).contiguous().to(self.device)
+        self.weights = None if v is None else v.to(torch.float32).contiguous().to(self.device)
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, want='report')               # (the energies do not depend on var)
+        return _decode_report(report, capi.ENVELOPE_REPORT, capi.ENVELOPE_COUNTS)
+
+    def distance_of(self, x):
+        """[B, N] float32 on the potential's device: the soft distance a_n of every residue of every sample of x [B,N,3] to the envelope."""
+        return self._launch(self._checked(x), self._one, want='distance')[0]
+
+    def gap_of(self, x):
+        """[B, M] float32 on the potential's device: the soft distance c_m of every envelope point to every sample of x [B,N,3]."""
+        return self._launch(self._checked(x), self._one, want='gap')[0]
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous): (logp, grad), (report [B, 6],), (distance_out [B, N],) or (gap_out [B, M],)
+        as `want` says."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        outs = {'logp': lambda: [torch.empty(B, **f32), torch.empty_like(x), None, None, None],
+                'report': lambda: [None, None, torch.empty(B, len(capi.ENVELOPE_REPORT), **f32), None, None],
+                'distance': lambda: [None, None, None, torch.empty(B, self.n_res, **f32), None],
+                'gap': lambda: [None, None, None, None, torch.empty(B, self.M, **f32)]}[want]()
+        self._call('genie_envelope_potential', self._stream(), B, self.n_res, _ptr(x), self.M, _ptr(self.points), _ptr(self.weights),
+                   self.softness, self.inside_distance, self.inside_weight, self.cover_distance, self.cover_weight, _ptr(var),
+                   *(_ptr(t) for t in outs), *self._workspace(self.lib.genie_envelope_potential_work_bytes(B, self.n_res, self.M)))
+        return tuple(t for t in outs if t is not None)
+
+
 class SumPotential:
     """The sum of twisting functions: `SumPotential(a, b, ...)(x0, step) = a(x0, step) + b(x0, step) + ...`, added in that order.
     `locate` and `has_fit` are those of the first member that has a `locate` (MotifPotential); `describe` is the merge of the reports

@@ -812,6 +812,67 @@ int genie_burial_potential(genie_stream_t stream, int B, int N, const float* x0 
                            void* work, size_t work_bytes);
 size_t genie_burial_potential_work_bytes(int B, int N);
 
+/* The envelope potential of twisted-diffusion / SMC sampling with its gradient and a per-particle report, without a handle
+ * (csrc/envelope_kernels.hip): what shape the design should have.  An envelope is M points y_m (device, [M,3]) with weights v_m > 0
+ * (device, [M]; NULL: all 1), in the frame the sampler works in: the lattice points of a solid, the atoms of an existing protein, the
+ * pseudo-atoms of a low-resolution map.  The design is kept inside it and made to fill it, by a soft assignment in both directions.
+ * The reference has no counterpart.
+ * For particle b with C-alpha coordinates x_n, n = 0..N-1, tau = softness (A^2), eps = GENIE_ENVELOPE_EPS (0.1 A) and
+ * q_nm = |x_n - y_m|^2, always formed from the coordinate differences, never from expanded norms:
+ *   s_n = -tau log sum_m exp(-q_nm / tau)       (the soft minimum over the points)     a_n = sqrt(max(s_n, 0) + eps^2)
+ *   t_m = -tau log sum_n exp(-q_nm / tau)       (the soft minimum over the residues)   c_m = sqrt(max(t_m, 0) + eps^2)
+ *   stay inside:  h_n = max(0, a_n - inside_distance),   E_inside = inside_weight sum_n h_n^2
+ *   fill it:      g_m = max(0, c_m - cover_distance),    E_cover  = cover_weight (N / sum v) sum_m v_m g_m^2
+ *   logp_out[b] = -(E_inside + E_cover) / (2 var)
+ * With p_nm = exp((s_n - q_nm) / tau) and r_nm = exp((t_m - q_nm) / tau), both <= 1:
+ *   grad_out[b,n] = -(1/var) [ inside_weight (h_n / a_n) sum_m p_nm (x_n - y_m) + cover_weight (N / sum v) sum_m v_m (g_m / c_m) r_nm (x_n - y_m) ]
+ * Both distances exceed eps, so the clamp at s = 0 (t = 0) lies where the hinge is 0 and E is C^1.  Both log-sum-exps subtract the
+ * running minimum: no exponential is taken of a positive number, and a particle hundreds of Angstrom from the envelope -- where a
+ * design is at high noise -- underflows nothing.  A weight of 0 switches its term off: its energy is exactly 0 and its exponentials
+ * in the gradient are not taken.  `var` is one float in device memory; the likelihood is left unnormalised.  eps is the compile-time
+ * constant, not an argument.  report_out[b] holds GENIE_ENVELOPE_REPORT floats:
+ *   n_outside (residues with h_n > 0), max_outside (the largest h_n), n_uncovered (points with g_m > 0), max_uncovered (the largest
+ *   g_m), e_envelope_inside (E_inside), e_envelope_cover (E_cover) (weighted, before the division by 2 var; counts stored as floats).
+ * distance_out [B,N], optional, receives the a_n; gap_out [B,M], optional, the c_m.  logp_out and grad_out are given together or both
+ * NULL; the others may be given alone; at least one output is asked for.
+ * Three launches on `stream`, the second only with grad_out, the third only with logp_out or report_out.  Soft minima: grid
+ * (ceil(N / 64) + ceil(M / 64), B), W waves: one loop with the roles swapped -- a work-group owns 64 residues, one per lane, and
+ * walks the points, or owns 64 points and walks the particle's residues.  The walked side is staged through 16 KiB of LDS in chunks
+ * of GENIE_ENVELOPE_CHUNK rows; each of the W waves takes a contiguous W-th of a chunk (wave-uniform row: an LDS broadcast),
+ * first for its smallest q, then for the sum of exp((min - q) / tau); a lane carries a (running minimum, rescaled sum) pair and the waves'
+ * pairs are merged in wave order.  s_n, t_m, the coefficients cover_weight (N / sum v) v_m g_m / c_m and three sums per tile go to
+ * `work`.  Gather: grid (ceil(N / 64), B): lane n walks the points again, staged with t_m and the coefficient, and skips the
+ * exponential of p_nm where h_n = 0 and that of r_nm where the point's coefficient is 0.  Finish: grid (B): the tile sums are added
+ * in tile order; logp and the report.  W = 16, so that the few work-groups of a small batch finish their serial walks sooner (B = 8,
+ * N = 256, M = 2048: 288 work-groups on 256 compute units); a launch of GENIE_ENVELOPE_FILL work-groups or more fills the device
+ * without that and uses W = 4.  The choice depends on B, N and M alone, so equal calls stay bitwise equal; a particle's last bits
+ * may differ between batch sizes on either side of the threshold.  B N M exponentials for each soft minimum and at most 2 B N M for the gather.  `work` holds
+ * N + 2 M + 3 (ceil(N / 64) + ceil(M / 64)) floats per particle (genie_envelope_potential_work_bytes(B, N, M), 4-byte aligned; 0 for
+ * sizes this entry refuses).  No allocation, no synchronisation, no host read, no atomics, no scatter: every output is written once
+ * in a fixed order, so two calls on the same inputs are bitwise equal.
+ * Limits.  No LDS or register limit bounds N or M, since the walked side is staged in chunks.  B <= 65535 is the grid's y extent.
+ * N <= GENIE_ENVELOPE_MAX_LENGTH (4096) and M <= GENIE_ENVELOPE_MAX_POINTS (16384) bound the time of a call -- at both limits one
+ * particle takes 2^28 exponentials on the quarter-rate transcendental pipe -- and the finishing step's tile table (320 tiles, 3840
+ * bytes of LDS).
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B outside
+ * 1..65535; N outside 1..GENIE_ENVELOPE_MAX_LENGTH; M outside 1..GENIE_ENVELOPE_MAX_POINTS; x0, points or var NULL; softness not
+ * finite or <= 0; inside_distance or cover_distance not finite or <= eps; a negative or non-finite weight; both weights 0; no output
+ * asked for; logp_out and grad_out not given together; `work` NULL, misaligned or work_bytes too small.  The caller validates the
+ * point weights (finite, > 0). */
+#define GENIE_ENVELOPE_REPORT 6   /* n_outside, max_outside, n_uncovered, max_uncovered, e_envelope_inside, e_envelope_cover */
+#define GENIE_ENVELOPE_EPS 0.1f
+#define GENIE_ENVELOPE_CHUNK 1024
+#define GENIE_ENVELOPE_FILL 2048  /* work-groups of a launch from which it runs 4 waves per work-group instead of 16 */
+#define GENIE_ENVELOPE_MAX_LENGTH 4096
+#define GENIE_ENVELOPE_MAX_POINTS 16384
+int genie_envelope_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int M, const float* points /*[M,3], device*/,
+                             const float* weights /*[M], device, or NULL: all 1*/, float softness, float inside_distance,
+                             float inside_weight, float cover_distance, float cover_weight, const float* var /*[1], device*/,
+                             float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                             float* report_out /*[B,GENIE_ENVELOPE_REPORT] or NULL*/, float* distance_out /*[B,N] or NULL: the a_n*/,
+                             float* gap_out /*[B,M] or NULL: the c_m*/, void* work, size_t work_bytes);
+size_t genie_envelope_potential_work_bytes(int B, int N, int M);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
