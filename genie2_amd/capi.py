@@ -141,6 +141,9 @@ SYMBOLS = {
     'genie_envelope_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_float] * 5 +
                                  [C.c_void_p] * 7 + [C.c_size_t]),
     'genie_envelope_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'genie_context_potential': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] +
+                                [C.c_float] * 6 + [C.c_void_p] * 6 + [C.c_size_t]),
+    'genie_context_potential_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
 }
 
 MOTIF_MAX_GROUPS = 8       # GENIE_MOTIF_MAX_GROUPS of include/genie_hip.h
@@ -186,6 +189,10 @@ ENVELOPE_COUNTS = ('n_outside', 'n_uncovered')
 ENVELOPE_EPS, ENVELOPE_CHUNK = 0.1, 1024        # GENIE_ENVELOPE_EPS, GENIE_ENVELOPE_CHUNK: the rows of the walked side staged in LDS at a time
 ENVELOPE_FILL = 2048        # GENIE_ENVELOPE_FILL: work-groups of a launch from which it runs 4 waves per work-group instead of 16
 ENVELOPE_MAX_LENGTH, ENVELOPE_MAX_POINTS = 4096, 16384      # GENIE_ENVELOPE_MAX_LENGTH, _MAX_POINTS
+CONTEXT_REPORT = ('context_contacts', 'n_context_contacts', 'n_context_interface', 'context_min_distance', 'n_context_clash', 'anchor_rmsd',
+                  'e_context_clash', 'e_context_contact')      # GENIE_CONTEXT_REPORT slots
+CONTEXT_COUNTS = ('n_context_contacts', 'n_context_interface', 'n_context_clash')
+CONTEXT_MAX_ATOMS = 12690       # GENIE_CONTEXT_MAX_ATOMS: the longest context whose staging fits in the kernel's 160 KiB of LDS
 TMALIGN_NORMS = ('query', 'reference', 'shorter', 'longer')      # norm 0..3 of genie_tm_align and genie_fold_align_potential
 
 _lib = None

@@ -70,13 +70,28 @@ positions of the design, not of the motif: a motif's placement moves per particl
 `--envelope_inside_weight`, `--envelope_cover_distance`, `--envelope_cover_weight`, `--envelope_softness`, `--envelope_tausq` and
 `--write_envelope`: the flags of add_envelope_arguments in the same module) add envelope guidance -- the design stays inside a given 3D
 shape and fills it -- summed after burial and before symmetry; `--write_envelope` writes outdir/envelope/ as that CLI does.  The
-envelope does not follow the motif's placement either."""
+envelope does not follow the motif's placement either.
+
+`--context_pdb FILE` (with `--context_chains`, `--context_clash_distance`, `--context_clash_weight`, `--context_contact_distance`,
+`--context_contacts_min`, `--context_contacts_max`, `--context_contacts_weight`, `--context_group`, `--context_tausq`, `--write_context`
+and `--write_context_complex`: the flags of add_context_arguments in the same module, which this CLI alone takes) adds the one term
+that does follow the motif: the C-alpha atoms of the motif's binding partner, given in the frame of the motif file's ATOM records
+(typically the complex the motif was cut from), are placed for every particle by the superposition of the motif on that particle's
+best placement and kept clear of, or in contact with, the rest of the design (ContextPotential, csrc/context_kernels.hip), summed
+right after the motif term.  It works with either `--align`: the fit it uses is always the superposed one, so the motif needs three
+residues that are not on a line.  With `--motif_groups file` the context is tied to one group, `--context_group LABEL` (required when
+there is more than one).  `--write_context` writes outdir/context/{length}_{index}.txt, one `key value` line per report field, and
+`--write_context_complex` outdir/context_complex/{length}_{index}.pdb: the context's chains as placed for that design, then the design
+as the last chain.  The defaults are design choices whose effect on sample quality is unmeasured (no trained checkpoint is in the
+tree)."""
 import os
 
+from . import capi
 from .motif import load_motif_spec
 from .sample_unconditional import PartialParser, UnconditionalRunner, add_common_arguments
-from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_burial_arguments, add_diversity_arguments, add_envelope_arguments, add_fold_arguments, add_guidance_arguments,
-                                         add_secstruct_arguments, add_shape_arguments, add_sheet_arguments, add_symmetry_arguments)
+from .sample_unconditional_shape import (GuidedRunner, add_binder_arguments, add_burial_arguments, add_context_arguments, add_diversity_arguments, add_envelope_arguments,
+                                         add_fold_arguments, add_guidance_arguments, add_secstruct_arguments, add_shape_arguments, add_sheet_arguments,
+                                         add_symmetry_arguments, context_constants, has_context_terms, report_fields, write_context_complex, write_context_report)
 
 
 def load_motif_segments(filepath):
@@ -119,6 +134,32 @@ def write_motif_locations(fit, directory, length, offset):
                     fh.write('# rmsd group {} {:.3f}\n'.format(label, value))
 
 
+def context_segments(constants):
+    """The indices of the motif segments a context is tied to: all of them, or with --motif_groups file those of --context_group
+    (of the only group when there is one).  A label the file does not have, a missing label with several groups, a label without
+    --motif_groups file and segments a superposition cannot use (fewer than 3 residues, or all on one line) end the run here."""
+    import torch
+    from .smc import _check_superposable, canonical_groups
+    segments, groups, label = constants['segments'], constants.get('groups'), constants.get('context_group')
+    if groups is None:
+        if label is not None:
+            raise SystemExit('--context_group needs --motif_groups file')
+        chosen = list(range(len(segments)))
+    else:
+        labels, index = canonical_groups(groups, len(segments))
+        if label is None and len(labels) > 1:
+            raise SystemExit('--context_pdb with --motif_groups file needs --context_group, one of %s' % ', '.join(map(str, labels)))
+        if label is not None and label not in [str(v) for v in labels]:
+            raise SystemExit('--context_group %s: the motif file has the groups %s' % (label, ', '.join(map(str, labels))))
+        g = 0 if label is None else [str(v) for v in labels].index(label)
+        chosen = [s for s, k in enumerate(index) if k == g]
+    try:
+        _check_superposable(torch.tensor([xyz for s in chosen for xyz in segments[s]], dtype=torch.float64), ' the context is tied to')
+    except ValueError as e:
+        raise SystemExit('--context_pdb: %s' % e) from None
+    return chosen
+
+
 class MotifRunner(GuidedRunner):
     def create_tasks(self, params):
         total = sum(len(s) for s in load_motif_segments(params['motif_file']))
@@ -136,17 +177,35 @@ class MotifRunner(GuidedRunner):
         c['segments'] = load_motif_segments(params['motif_file'])
         c['motif_groups'] = params.get('motif_groups', 'joint')
         c['groups'] = load_motif_groups(params['motif_file']) if c['motif_groups'] == 'file' else None
+        c.update(context_constants(params))
+        c['context_segments'] = context_segments(c) if has_context_terms(c) else None
         return c
 
     def batch_potentials(self, constants, length, abar, device):
         # one MotifPotential per batch; its placements drawn from numpy's global generator, as the reference does
-        from .smc import MotifPotential
-        return (MotifPotential(constants['segments'], length, abar, tausq=constants['tausq'], max_offsets=constants['max_offsets'],
-                               device=device, align=constants['align'], groups=constants.get('groups')),)
+        from .smc import ContextPotential, MotifPotential
+        motif = MotifPotential(constants['segments'], length, abar, tausq=constants['tausq'], max_offsets=constants['max_offsets'],
+                               device=device, align=constants['align'], groups=constants.get('groups'))
+        self.context = None                                             # (the batch's own: after_batch reports with it)
+        if not has_context_terms(constants):
+            return (motif,)
+        anchors = [xyz for s in constants['context_segments'] for xyz in constants['segments'][s]]
+        self.context = ContextPotential(length, abar, anchors, constants['context']['xyz'], motif=motif, segments=constants['context_segments'],
+                                        clash_distance=constants['context_clash_distance'], clash_weight=constants['context_clash_weight'],
+                                        contact_distance=constants['context_contact_distance'], contacts=constants['context_contacts'],
+                                        contacts_weight=constants['context_contacts_weight'], tausq=constants['context_tausq'], device=device)
+        return (motif, self.context)
 
     def after_batch(self, constants, sampler, length, offset):
         if constants['write_motif_locations']:
             write_motif_locations(sampler.last_fit, os.path.join(constants['outdir'], 'motif_locations'), length, offset)
+        context = getattr(self, 'context', None)
+        if constants.get('write_context') and context is not None:
+            write_context_report(report_fields(sampler.last_shape, capi.CONTEXT_REPORT), os.path.join(constants['outdir'], 'context'), length, offset)
+        if constants.get('write_context_complex') and context is not None:
+            placed = context.placed_context(sampler.last_positions.to(context.device)).cpu().numpy()
+            write_context_complex(sampler.last_positions.numpy(), placed, constants['context'], os.path.join(constants['outdir'], 'context_complex'),
+                                  length, offset)
 
 
 def build_parser():
@@ -178,6 +237,7 @@ def build_parser():
     add_diversity_arguments(p)
     add_burial_arguments(p)
     add_envelope_arguments(p)
+    add_context_arguments(p)
     return p
 
 

@@ -542,6 +542,90 @@ def write_complex(positions, target, directory, length, offset):
         F.save_np_features_to_pdb(f, os.path.join(directory, '{}_{}.pdb'.format(length, offset + i)))
 
 
+# The context flags of the motif CLI (sample_unconditional_motif.py: a context follows a motif's placement, so the shape CLI's parser
+# does not take them).  The defaults -- contact distance 8 A, weights 1, tausq 1 A^2 -- are design choices: no trained checkpoint is
+# in the tree, so their effect on sample quality is unmeasured.
+CONTEXT_DEFAULTS = dict(context_pdb=None, context_chains=None, context_clash_distance=None, context_clash_weight=1.0, context_contact_distance=8.0,
+                        context_contacts_min=None, context_contacts_max=None, context_contacts_weight=1.0, context_group=None, context_tausq=1.0,
+                        write_context=False, write_context_complex=False)
+
+
+def add_context_arguments(parser):
+    tail = ' (an addition to the reference CLI, like --motif_groups)'
+    parser.add_argument('--context_pdb', type=str, default=None,
+                        help='Guide the design relative to the C-alpha atoms of this structure, the binding partner of the motif, which '
+                             'follows every particle\'s own placement of the motif; it must be in the frame of the motif file\'s ATOM '
+                             'records, typically the complex the motif was cut from; default: no such term' + tail)
+    parser.add_argument('--context_chains', type=str, default=None, help='Chain letters of the context to use, e.g. HL; default: all' + tail)
+    parser.add_argument('--context_clash_distance', type=float, default=None,
+                        help='Guide design-context C-alpha pairs apart that are closer than this many Angstrom (motif residues sit '
+                             'out); default: no such term' + tail)
+    parser.add_argument('--context_clash_weight', type=float, default=1.0, help='Weight of the context clash term' + tail)
+    parser.add_argument('--context_contact_distance', type=float, default=8.0,
+                        help='C-alpha distance in Angstrom at which a design-context pair counts half a contact' + tail)
+    parser.add_argument('--context_contacts_min', type=float, default=None,
+                        help='Guide the soft number of design-context contacts above this; default: no such bound' + tail)
+    parser.add_argument('--context_contacts_max', type=float, default=None,
+                        help='Guide the soft number of design-context contacts below this; default: no such bound' + tail)
+    parser.add_argument('--context_contacts_weight', type=float, default=1.0, help='Weight of the context contact-count term' + tail)
+    parser.add_argument('--context_group', type=str, default=None,
+                        help='With --motif_groups file: the label of the motif group the context is tied to (required when the file has '
+                             'more than one group)' + tail)
+    parser.add_argument('--context_tausq', type=float, default=1.0, help='Likelihood variance tau^2 of the context terms, Angstrom^2' + tail)
+    parser.add_argument('--write_context', action='store_true',
+                        help='Write outdir/context/{length}_{index}.txt: contacts, interface size, closest approach, clashes, the anchor '
+                             'RMSD and the energies of every written structure against the context as placed for it' + tail)
+    parser.add_argument('--write_context_complex', action='store_true',
+                        help='Write outdir/context_complex/{length}_{index}.pdb: the context chains as placed for that design, then the '
+                             'design as the last chain' + tail)
+
+
+def context_constants(params):
+    """The context keys of a runner's constants: the flags of add_context_arguments; with --context_pdb also 'context', the file read
+    and ready to travel to a worker process -- 'xyz' float64 numpy [C, 3] in the file's frame, 'labels', 'chain_lengths', 'aatype'
+    numpy [C] -- and 'context_contacts' = (min, max) or None (one of the two given: the other is 0 / inf).  A context flag without
+    --context_pdb, a context with no term, and a file or chain that does not hold up end the run here."""
+    import math
+    from .smc import load_target
+    c = {k: params.get(k, v) for k, v in CONTEXT_DEFAULTS.items()}
+    c['write_context'], c['write_context_complex'] = bool(c['write_context']), bool(c['write_context_complex'])
+    c['context'] = c['context_contacts'] = None
+    if c['context_pdb'] is None:
+        given = [k for k, v in CONTEXT_DEFAULTS.items() if c[k] != v]
+        if given:
+            raise SystemExit('%s: a context flag needs --context_pdb, the structure it is about' % ', '.join('--' + k for k in given))
+        return c
+    lo, hi = c['context_contacts_min'], c['context_contacts_max']
+    c['context_contacts'] = None if lo is None and hi is None else (0.0 if lo is None else lo, math.inf if hi is None else hi)
+    if c['context_contacts'] is None and c['context_clash_distance'] is None:
+        raise SystemExit('--context_pdb needs a term: --context_clash_distance, --context_contacts_min or --context_contacts_max')
+    try:
+        xyz, labels, chain_lengths, aatype = load_target(c['context_pdb'], c['context_chains'])
+    except (OSError, ValueError) as e:
+        raise SystemExit('--context_pdb / --context_chains: %s' % e) from None
+    c['context'] = dict(xyz=xyz.numpy(), labels=labels, chain_lengths=chain_lengths, aatype=aatype.numpy())
+    return c
+
+
+def has_context_terms(constants):
+    return constants.get('context') is not None
+
+
+def write_context_report(report, directory, length, offset):
+    """One file per sample of a batch, {length}_{offset + i}.txt: a `key value` line per field of `report` (the context fields of
+    last_shape), %.3f for contacts, distances and energies, %d for counts."""
+    from .capi import CONTEXT_COUNTS
+    write_report(report, CONTEXT_COUNTS, directory, length, offset)
+
+
+def write_context_complex(positions, placed, context, directory, length, offset):
+    """write_complex for a context that moves: file {length}_{offset + i}.pdb holds the context's chains (context_constants' context)
+    at placed[i] [C, 3], where ContextPotential.placed_context puts them for design i, then positions[i] as the last chain."""
+    import numpy as np
+    for i, (design, xyz) in enumerate(zip(np.asarray(positions, dtype=float), np.asarray(placed, dtype=float))):
+        write_complex(design[None], dict(context, xyz=xyz), directory, length, offset + i)
+
+
 FOLD_DEFAULTS = dict(template_pdb=None, template_tm_min=0.6, template_weight=1.0, avoid_dir=None, avoid_tm_max=0.5, avoid_weight=1.0,
                      avoid_representatives=False, fold_iterations=16, fold_tausq=1.0, write_fold=False)
 FOLD_MAX_REFERENCES = 4096      # capi.FOLD_MAX_REFERENCES: the most references of one length

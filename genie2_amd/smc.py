@@ -1470,6 +1470,187 @@ class BinderPotential(_HipPotential):
         return tuple(t for t in outs if t is not None)
 
 
+def check_anchor_index(anchor_index, n_anchors, n_res):
+    """Anchor residues as an int32 tensor [rows, n_anchors] -- one row for every particle, or [n_anchors] for one row that serves all
+    -- of integers in 0..n_res-1, distinct within a row; a ValueError otherwise."""
+    try:
+        rows = anchor_index.tolist() if torch.is_tensor(anchor_index) else list(anchor_index)
+        rows = [list(r) for r in rows] if rows and isinstance(rows[0], (list, tuple)) else [list(rows)]
+    except TypeError:
+        raise ValueError('anchor_index must be a list of design residue indices, got %r' % (anchor_index,)) from None
+    for row in rows:
+        if len(row) != n_anchors:
+            raise ValueError('anchor_index has %d residues in a row, anchor_xyz has %d' % (len(row), n_anchors))
+        for i in row:
+            if isinstance(i, bool) or not isinstance(i, numbers.Integral) or not 0 <= i < n_res:
+                raise ValueError('anchor_index %r is not an integer in 0..%d' % (i, n_res - 1))
+        if len(set(row)) != len(row):
+            raise ValueError('anchor_index lists a residue twice: %r' % (row,))
+    return torch.tensor(rows, dtype=torch.int32).reshape(len(rows), n_anchors)
+
+
+class ContextPotential(_HipPotential):
+    """Context guidance as one HIP entry (genie_context_potential, csrc/context_kernels.hip; include/genie_hip.h states the
+    mathematics): `pot(x0 [B,N,3], step) -> log p [B]`, differentiable in x0, a drop-in `twisting_function` for TwistedSampler beside
+    the other built-in potentials (SumPotential adds them).  A context is the binding partner of a motif: `context` [C, 3], C-alpha
+    coordinates in the same frame as `anchor_xyz` [A, 3], the motif residues it is tied to (the motif file's frame; this class keeps
+    its own copies and does not depend on how MotifPotential centres its target).  For every particle the anchors are superposed on
+    the design residues that hold them, the fitted rigid motion places the context, and the placed context is scored against the rest
+    of the design -- the anchors sit out -- with BinderPotential's clash and contact terms:
+      clash_distance   every design-context pair closer than this many Angstrom (None: off), weighted clash_weight;
+      contacts         (min, max): the soft number of contacts sum 1 / (1 + (d / contact_distance)^6) is kept in that range (None:
+                       off; max may be inf), weighted contacts_weight.
+    log p = -(E_clash + E_contact) / (2 var), var = xstart_variance(alphas_cumprod[step], tausq) computed on the device.  The gradient
+    is exact, the part that flows through the fitted rotation included: the partner is a long lever on a small motif.
+
+    Exactly one of two arguments says where the anchors are:
+      anchor_index     A design residues (or one row of A per particle, [B, A]): a known placement;
+      motif            a MotifPotential, with `segments`, the indices of its segments that `anchor_xyz` lists, in order (None: all of
+                       them; with motif groups, the segments of exactly one group).  Every call first runs the motif's superposed fit
+                       (MotifPotential.locate's) and takes the anchors from each particle's best placement, with device tensor
+                       operations.  Which placement that is is held fixed within a call: the function is piecewise in x across a
+                       change of best placement, as AlignedFoldPotential is across a change of alignment.
+    Nothing on the per-step path reads device memory from the host.
+
+    Everything is validated on the host before the device is looked at; a potential with no term enabled and collinear anchors are
+    ValueErrors.  `describe(x)` reports every sample of x with the names of capi.CONTEXT_REPORT: 'context_contacts',
+    'n_context_contacts', 'n_context_interface', 'context_min_distance', 'n_context_clash' (int64 counts), 'anchor_rmsd' (of the
+    superposition), 'e_context_clash', 'e_context_contact' (the weighted energies, before the division by 2 var).  `pose_of(x)` is
+    (R [B,3,3], t [B,3]) with placed = R y + t, `placed_context(x)` the placed context [B, C, 3].
+
+    The defaults (tausq = 1 A^2, contact_distance 8 A, weights 1) are design choices: no trained checkpoint is in the tree, so their
+    effect on sample quality is unmeasured.  Only C-alpha atoms are seen, and the denoiser never sees the context."""
+
+    def __init__(self, n_res, alphas_cumprod, anchor_xyz, context, anchor_index=None, motif=None, segments=None, clash_distance=None,
+                 clash_weight=1.0, contact_distance=8.0, contacts=None, contacts_weight=1.0, tausq=1.0, device='cuda'):
+        import math
+        if isinstance(n_res, bool) or not isinstance(n_res, numbers.Integral) or n_res < 1:
+            raise ValueError('n_res must be an integer >= 1, got %r' % (n_res,))
+        coords = {}
+        for name, v, low in (('anchor_xyz', anchor_xyz, 3), ('context', context, 1)):
+            try:
+                c = torch.as_tensor(v).detach().to(dtype=torch.float32, device='cpu')
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError('%s must be [n, 3] coordinates, got %r' % (name, type(v))) from None
+            if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] < low:
+                raise ValueError('%s must be [n, 3] with n >= %d, got %s' % (name, low, tuple(c.shape)))
+            if not bool(torch.isfinite(c).all()):
+                raise ValueError('%s has a coordinate that is not finite' % name)
+            coords[name] = c.contiguous()
+        t, y = coords['anchor_xyz'], coords['context']
+        if t.shape[0] > n_res:
+            raise ValueError('anchor_xyz has %d residues, the design %d' % (t.shape[0], n_res))
+        if y.shape[0] > capi.CONTEXT_MAX_ATOMS:
+            raise ValueError('context has %d atoms, at most %d fit in the LDS of the kernel' % (y.shape[0], capi.CONTEXT_MAX_ATOMS))
+        try:
+            _check_superposable(t, ' of anchor_xyz')
+        except ValueError as e:
+            raise ValueError('anchor_xyz: %s' % e) from None
+        if (anchor_index is None) == (motif is None):
+            raise ValueError('give exactly one of anchor_index and motif')
+        if motif is None and segments is not None:
+            raise ValueError('segments goes with motif')
+        self.motif = motif
+        if motif is None:
+            rows = check_anchor_index(anchor_index, int(t.shape[0]), n_res)
+        else:
+            if not isinstance(motif, MotifPotential):
+                raise ValueError('motif must be a MotifPotential, got %r' % (type(motif),))
+            if motif.n_res != n_res:
+                raise ValueError('motif places its segments in %d residues, n_res is %d' % (motif.n_res, n_res))
+            if not motif.has_fit:
+                raise ValueError('motif has no superposed fit (3 motif residues at least, in every group)')
+            try:
+                segs = list(range(motif.S)) if segments is None else [s for s in segments]
+            except TypeError:
+                raise ValueError('segments must be a list of segment indices of motif, got %r' % (segments,)) from None
+            for s in segs:
+                if isinstance(s, bool) or not isinstance(s, numbers.Integral) or not 0 <= s < motif.S:
+                    raise ValueError('segments: %r is not an integer in 0..%d' % (s, motif.S - 1))
+            if not segs or len(set(segs)) != len(segs):
+                raise ValueError('segments must be distinct and at least one, got %r' % (segs,))
+            if motif.groups is not None:
+                of = sorted({motif.seg_group[s] for s in segs})
+                if len(of) != 1 or sorted(segs) != [s for s, g in enumerate(motif.seg_group) if g == of[0]]:
+                    raise ValueError('segments must be the segments of exactly one motif group (motif has groups %r), got %r'
+                                     % (motif.groups, segs))
+            if sum(motif.seg_len[s] for s in segs) != t.shape[0]:
+                raise ValueError('anchor_xyz has %d residues, segments %r of motif have %d'
+                                 % (t.shape[0], segs, sum(motif.seg_len[s] for s in segs)))
+            self.segments = [int(s) for s in segs]
+        for name, v in (('clash_distance', clash_distance), ('clash_weight', clash_weight), ('contact_distance', contact_distance),
+                        ('contacts_weight', contacts_weight)):
+            if v is not None and not (_is_scalar(v) and math.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError('%s must be finite and >= 0, got %r' % (name, v))
+        if contact_distance is None or not float(contact_distance) > 0:
+            raise ValueError('contact_distance must be > 0, got %r' % (contact_distance,))
+        if contacts is not None:
+            try:
+                lo, hi = (float(v) for v in contacts)
+            except (TypeError, ValueError):
+                raise ValueError('contacts must be (min, max), got %r' % (contacts,)) from None
+            if not (math.isfinite(lo) and lo >= 0 and hi >= lo):
+                raise ValueError('contacts must be (min, max) with 0 <= min <= max, min finite, got %r' % (contacts,))
+        if not (_is_scalar(tausq) and math.isfinite(float(tausq)) and float(tausq) > 0):
+            raise ValueError('tausq must be finite and > 0, got %r' % (tausq,))
+        if clash_distance is None and contacts is None:
+            raise ValueError('no term enabled: give clash_distance or contacts')
+        # a term that is off is a weight of 0 to the entry
+        self.clash_distance, self.clash_weight = (0.0, 0.0) if clash_distance is None else (float(clash_distance), float(clash_weight))
+        self.contact_distance = float(contact_distance)
+        self.contacts, self.contacts_weight = ((0.0, math.inf), 0.0) if contacts is None else ((lo, hi), float(contacts_weight))
+        super().__init__(n_res, alphas_cumprod, tausq, device)
+        if motif is not None and motif.device != self.device:
+            raise ValueError('motif is on %s, the potential on %s' % (motif.device, self.device))
+        self.A, self.C = int(t.shape[0]), int(y.shape[0])
+        self.anchor_xyz, self.context = t.to(self.device), y.to(self.device)
+        if motif is None:
+            self.anchor_index = rows.to(self.device)
+        else:                                                           # anchor k is residue _anchor_offset[k] of segment _anchor_segment[k]
+            self._anchor_segment = torch.tensor([s for s in self.segments for _ in range(motif.seg_len[s])], dtype=torch.int64, device=self.device)
+            self._anchor_offset = torch.tensor([i for s in self.segments for i in range(motif.seg_len[s])], dtype=torch.int32, device=self.device)
+
+    def anchors_of(self, x):
+        """[B, A] int32 on the potential's device: the design residues that hold the anchors in every sample of x (f32, contiguous,
+        checked) -- the given ones, or those of the motif's best placement after optimal superposition.  No host read."""
+        B = x.shape[0]
+        if self.motif is None:
+            if self.anchor_index.shape[0] not in (1, B):
+                raise ValueError('anchor_index has %d rows, x0 %d particles' % (self.anchor_index.shape[0], B))
+            return self.anchor_index.expand(B, self.A).contiguous()
+        best = self.motif._launch(x, self.motif._one, fit=True)[0]
+        starts = self.motif.starts.index_select(0, best.long())         # [B, S]
+        return (starts.index_select(1, self._anchor_segment) + self._anchor_offset[None]).contiguous()
+
+    def describe(self, x):
+        """The report of every sample of x [B,N,3] (the class docstring), on the potential's device."""
+        report, = self._launch(self._checked(x), self._one, want='report')               # (the energies do not depend on var)
+        return _decode_report(report, capi.CONTEXT_REPORT, capi.CONTEXT_COUNTS)
+
+    def pose_of(self, x):
+        """(R [B,3,3], t [B,3]) float32 on the potential's device: the fitted motion of every sample of x [B,N,3], placed = R y + t."""
+        pose, = self._launch(self._checked(x), self._one, want='pose')
+        return pose[:, :9].reshape(-1, 3, 3).clone(), pose[:, 9:].clone()
+
+    def placed_context(self, x):
+        """[B, C, 3] float32 on the potential's device: the context as placed for every sample of x [B,N,3]."""
+        R, t = self.pose_of(x)
+        return torch.einsum('bij,cj->bci', R, self.context) + t[:, None]
+
+    def _launch(self, x, var, want='logp'):
+        """One call of the C entry on x (f32, contiguous): (logp, grad), (report [B, 8],) or (pose [B, 12],) as `want` says."""
+        B, f32 = x.shape[0], dict(dtype=torch.float32, device=x.device)
+        outs = {'logp': lambda: [torch.empty(B, **f32), torch.empty_like(x), None, None],
+                'report': lambda: [None, None, torch.empty(B, len(capi.CONTEXT_REPORT), **f32), None],
+                'pose': lambda: [None, None, None, torch.empty(B, 12, **f32)]}[want]()
+        index = self.anchors_of(x)
+        self._call('genie_context_potential', self._stream(), B, self.n_res, _ptr(x), self.A, _ptr(index), _ptr(self.anchor_xyz), self.C,
+                   _ptr(self.context), self.clash_distance, self.clash_weight, self.contact_distance, self.contacts[0], self.contacts[1],
+                   self.contacts_weight, _ptr(var), *(_ptr(t) for t in outs),
+                   *self._workspace(self.lib.genie_context_potential_work_bytes(B, self.n_res)))
+        return tuple(t for t in outs if t is not None)
+
+
 def check_fold_bounds(bounds, n_refs):
     """Per-reference rows (lo, hi, weight) -- or (lo, hi): weight 1 -- as a float64 tensor [n_refs, 3]: TM-scores to stay between,
     0 <= lo <= hi, lo finite, hi possibly inf, weight finite and >= 0; a ValueError otherwise."""

@@ -873,6 +873,74 @@ int genie_envelope_potential(genie_stream_t stream, int B, int N, const float* x
                              float* gap_out /*[B,M] or NULL: the c_m*/, void* work, size_t work_bytes);
 size_t genie_envelope_potential_work_bytes(int B, int N, int M);
 
+/* The context potential of twisted-diffusion / SMC sampling with its gradient, a per-particle report and the fitted pose, without a
+ * handle (csrc/context_kernels.hip): a binding partner that follows each particle's own placement of the motif.  The motif's anchors
+ * are superposed on the design residues that hold them, the fitted rigid motion places the partner's C-alpha atoms (the context),
+ * and the placed context is scored against the rest of the design with genie_binder_potential's clash and contact terms.  The
+ * reference has no counterpart.
+ * anchor_index [B,A] (device int32) names, per particle, the A distinct design residues idx[k] that hold the anchors; anchor_xyz
+ * [A,3] are the anchors' coordinates t_k and context [C,3] the context's y_c, both in one frame (the motif file's; device memory).
+ * For particle b with coordinates x_n, n = 0..N-1:
+ *   a_k = x_idx[k],  abar = mean_k a_k,  tbar = mean_k t_k
+ *   S   = sum_k (t_k - tbar)(a_k - abar)^T                         (S_ab = sum t_a c_b)
+ *   q   = the unit eigenvector of the largest eigenvalue lam_0 of Horn's symmetric 4x4 K(S), float32 Jacobi (csrc/horn.h: mr_eigen),
+ *   R   = R(q), the proper rotation that minimises sum_k |R (t_k - tbar) - (a_k - abar)|^2
+ *   y'_c = R (y_c - tbar) + abar                                   (the context as placed for this particle)
+ *   anchor_rmsd = sqrt(mean_k |R (t_k - tbar) - (a_k - abar)|^2)
+ *   over the pairs (n, c) with n NOT an anchor:  d = |x_n - y'_c|,  s(d) = 1 / (1 + (d / contact_distance)^6)
+ *   E_clash   = clash_weight    * sum max(0, clash_distance - d)^2
+ *   Cc        = sum s(d)
+ *   E_contact = contacts_weight * ( max(0, contacts_min - Cc)^2 + max(0, Cc - contacts_max)^2 )    (contacts_max may be +inf)
+ *   logp_out[b] = -(E_clash + E_contact) / (2 var)
+ * Anchors are left out of the pair sums: the geometry between motif and partner is given.  grad_out[b,n] = d logp[b] / d x_n is the
+ * exact gradient of this function with the anchor rows held fixed.  With p_nc the force of pair (n, c) on x_n,
+ *   p_nc = clash_weight (clash_distance - d)_+ (x_n - y'_c) / d + 6 k / contact_distance^2 r^4 s^2 (x_n - y'_c),
+ *   k = contacts_weight ((Cc - contacts_max)_+ - (contacts_min - Cc)_+),  r = d / contact_distance
+ * (0 for a clash pair with d exactly 0), P = sum_nc p_nc and M = sum_nc p_nc (y'_c - abar)^T:
+ *   grad[b,n]      = (1/var) sum_c p_nc                                        for n not an anchor
+ *   grad[b,idx[k]] = (1/var) ( -P / A + D^T (t_k - tbar) )                     for the anchors
+ * where D = dE/dS follows from G_R = -M R (the derivative with respect to R: the reaction -p_nc on y'_c times (y_c - tbar)^T) by
+ * first-order perturbation of the top eigenvector (csrc/horn.h: mr_fit_adjoint): g = dR/dq : G_R without its component along q,
+ * z = sum_{i=1..3} v_i (v_i . g) / (lam_0 - lam_i) over the three other eigenpairs, dE/dK_ij = z_i q_j, and K is linear in S.  An
+ * eigenpair with lam_0 - lam_i not above 1e-6 lam_0 (MR_GAP_FLOOR) contributes 0: a degenerate fit (anchors on one line, or all
+ * at one point) has no unique rotation, and every output stays finite.  Net force and net torque of the gradient are 0.
+ * report_out[b] holds GENIE_CONTEXT_REPORT floats:
+ *   context_contacts (Cc), n_context_contacts (pairs with d < contact_distance), n_context_interface (design residues, anchors
+ *   excluded, with some context atom closer than contact_distance), context_min_distance (the smallest d; +inf when A = N leaves no
+ *   pair), n_context_clash (pairs with d < clash_distance), anchor_rmsd, e_context_clash, e_context_contact (the weighted E above,
+ *   before the division by 2 var)
+ * (counts are stored as floats: exact up to 2^24; the names differ from the binder report's, so that a merged report keeps both).
+ * pose_out[b], optional, receives R row-major and then the translation abar - R tbar: y' = R y + t.  logp_out and grad_out are given
+ * together or both NULL; report_out and pose_out may be given alone (pose_out alone runs the fit only); at least one output is asked
+ * for.  A weight of 0 switches its term off, energy and force.
+ * The anchor rows are checked on the device: a row with an index outside 0..N-1 (clamped before it is used as an address) or with an
+ * index given twice flags its particle, which gets logp 0, a gradient of 0, a report of 0 and the identity pose.
+ * Three launches on `stream`.  The fit: grid B, one wave per particle, lanes striding over the anchors; it leaves R, abar, tbar, the
+ * four eigenpairs, anchor_rmsd, the flag and a residue-to-anchor map in `work`.  The pairs: grid (ceil(N / 64), B), 256 threads;
+ * every work-group stages R (y_c - tbar) in dynamic LDS (12 C + 11 552 bytes; above 64 KiB the kernel's limit is raised) and takes 64
+ * design residues, one per lane; each wave walks a contiguous quarter of the context in partial sums of 64, every lane keeping the
+ * 2 x 9 moments of p_nc beside the binder kernel's sums; each residue's unscaled clash and contact force and the tile's 30 partial
+ * values go to `work` (genie_context_potential_work_bytes(B, N) = 4 B (40 + 7 N + 32 ceil(N / 64)) bytes, 4-byte aligned).  The
+ * finish: the same grid with 64 threads adds the tiles in tile order, forms k, P, M and D, and writes logp, the report and the
+ * gradient, an anchor its share instead of a direct force.  No allocation, no synchronisation, no host read, no atomics, no scatter:
+ * every output is written once in a fixed order, so two calls on the same inputs are bitwise equal.
+ * Returns GENIE_E_ARG, before the device is touched, with genie_last_error(NULL) naming this entry and the argument: B < 1 (or above
+ * 65535); N < 1; A outside 3..N; C < 1; x0, anchor_index, anchor_xyz, context or var NULL; a negative or non-finite distance, weight
+ * or count (contacts_max alone may be +inf); contacts_max below contacts_min; a contact_distance of 0; no output asked for; logp_out
+ * and grad_out not given together; `work` NULL, misaligned or work_bytes too small; a C whose staging does not fit in LDS (160 KiB:
+ * C above GENIE_CONTEXT_MAX_ATOMS). */
+#define GENIE_CONTEXT_REPORT 8   /* context_contacts, n_context_contacts, n_context_interface, context_min_distance, n_context_clash,
+                                    anchor_rmsd, e_context_clash, e_context_contact */
+#define GENIE_CONTEXT_MAX_ATOMS 12690
+int genie_context_potential(genie_stream_t stream, int B, int N, const float* x0 /*[B,N,3]*/, int A,
+                            const int32_t* anchor_index /*[B,A], device*/, const float* anchor_xyz /*[A,3], device*/, int C,
+                            const float* context /*[C,3], device*/, float clash_distance, float clash_weight, float contact_distance,
+                            float contacts_min, float contacts_max, float contacts_weight, const float* var /*[1], device*/,
+                            float* logp_out /*[B] or NULL*/, float* grad_out /*[B,N,3] or NULL*/,
+                            float* report_out /*[B,GENIE_CONTEXT_REPORT] or NULL*/, float* pose_out /*[B,12] or NULL*/, void* work,
+                            size_t work_bytes);
+size_t genie_context_potential_work_bytes(int B, int N);
+
 /* Denoiser.forward (genie/model/model.py:125-192): z_out[B,N,3].
  * timesteps: device int32 [B].  quat_codes: optional device int8 [B,N,N]
  * pinning the sign of each pair quaternion to the reference's eigh output
